@@ -11,11 +11,16 @@ round-robin, so up to four batches are in flight: the latency-bound kernels of
 one batch overlap those of the others, and the host tail (reconcile + sort by
 id) of batch k overlaps the kernels of the later ones.
 
-    python bench.py [--gpus N --steps K --warmup W --batch B]
+    python bench.py [--gpus N --steps K --warmup W --batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints one JSON line.  Latency: frames fed one at a time (B = 1) from
-HBM to detections in host memory.  cpu_baseline: the C oracle
+Rank 0 prints one JSON line.  A plain run does what the headline needs and no
+more: set-up, warm-up, the K timed steps, the line.  --dump-outputs DIR also
+writes what the last timed step returned (DIR/*.npy).  --full adds every other
+leg, each with its own option: the serialized stage profile, the isolated
+roofline pass, the latencies (frames fed one at a time, B = 1, to detections in
+host memory; the C3 batch of 4; the node's per-frame path), the host-ingest
+loop, the scatter leg of an N > 1 run, and cpu_baseline: the C oracle
 (oracle/ao_bench, restatement of the reference pipeline) on host cores.
 """
 import argparse
@@ -98,7 +103,51 @@ def parse(argv=None):
     ap.add_argument("--scatter-leg-steps", type=int, default=None,
                     help="N > 1 with --ingest local: steps of the scatter leg run after the timed region (the "
                          "north-star topology, reported as scatter_leg; default = --steps; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline (stage profile, isolated roofline pass, latencies, host "
+                         "ingest, node path, scatter leg, CPU baseline), each as its own option sets it; without "
+                         "--full none of them runs and their fields of the line are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to the caller as DIR/<name>.npy (float64): "
+                         "counts [frames], detections [n, 23], poses [n, 15] (see dump_outputs)")
     return ap.parse_args(argv)
+
+
+def headline_only(args):
+    """The legs beside the headline switched off (a run without --full)."""
+    args.no_stage_profile = args.no_cpu_baseline = True
+    args.latency_frames = args.c3_latency_iters = args.host_ingest_steps = 0
+    args.node_path_calls = args.isolated_batches = args.scatter_leg_steps = 0
+    return args
+
+
+DUMP_MAX_FRAMES = 1024  # of a larger batch the first 1024 frames are written (a 720p frame's rows: ~5 KB)
+
+
+def last_step_outputs(det, nframes):
+    """What the caller of the timed loop holds after its last step -- the batch in
+    `det`'s output buffer -- as float64 arrays:
+    counts [frames]: detections per frame;
+    detections [n, 23]: frame, id, hamming, decision_margin, H (9, row-major), c (2), p (4 x 2);
+    poses [n, 15]: frame, id, R (9, row-major), t (3), err -- in the order of `detections`."""
+    nf = min(nframes, DUMP_MAX_FRAMES)
+    res = det.results()
+    drows, prows = [], []
+    for f in range(nf):
+        for d in res[f]:
+            drows.append(np.concatenate(([f, d.id, d.hamming, d.decision_margin], d.H.ravel(), d.c, d.p.ravel())))
+        for p in det.poses(f):
+            prows.append(np.concatenate(([f, p.id], p.R.ravel(), p.t, [p.err])))
+    return {"counts": np.array([len(r) for r in res[:nf]], np.float64),
+            "detections": np.array(drows, np.float64).reshape(-1, 23),
+            "poses": np.array(prows, np.float64).reshape(-1, 15)}
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """DIR/<name>.npy (rank r of an N > 1 run: DIR/<name>_rank<r>.npy, its own shard's batch)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), a)
 
 
 def pool_copies(args):
@@ -412,6 +461,8 @@ def main():
             dist.destroy_process_group()
         return
 
+    if not args.full:
+        headline_only(args)
     run(max(1, args.warmup))
 
     # per-stage GPU time (HIP events between the kernels, serialized launch
@@ -448,6 +499,8 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     host1 = [d.batch_stats() for d in dets]
+    if args.dump_outputs:  # the last timed step's batch: still in the output buffer of the instance that ran it
+        dump_outputs(args.dump_outputs, last_step_outputs(dets[(args.steps - 1) % len(dets)], B), rank, world)
     kt = [d.kernel_time() for d in dets] if ktimer else [(0.0, 0)]
     k_launches = sum(n for _, n in kt)
     k_ms_events = sum(ms * n for ms, n in kt) / max(1, k_launches)
@@ -533,6 +586,10 @@ def main():
             lat_c3.append(time.perf_counter() - t1)
         c3.close()
     lat_c3 = np.array(lat_c3 or [0.0]) * 1e3
+
+    def pct(lat, q, measured):
+        """Percentile of a latency leg in ms; null when the leg did not run."""
+        return round(float(np.percentile(lat, q)), 4) if measured else None
 
     # the same loop fed from page-locked host frames: what a camera-fed GPU sustains
     host_ingest = None
@@ -652,13 +709,14 @@ def main():
                                    "to rank 0" % world) if scatter else
                                   "frame-sharded x%d (no data-path collective)" % world,
                    "ingest": "scatter" if scatter else "local"},
-        "p50_latency_ms": round(float(np.percentile(lat_h, 50)), 4),
-        "p99_latency_ms": round(float(np.percentile(lat_h, 99)), 4),
+        "full": args.full,
+        "p50_latency_ms": pct(lat_h, 50, args.latency_frames > 0),
+        "p99_latency_ms": pct(lat_h, 99, args.latency_frames > 0),
         "latency_note": "B=1, pageable host YUYV frame -> detections + poses in host memory",
-        "p50_latency_hbm_ms": round(float(np.percentile(lat_d, 50)), 4),
-        "p99_latency_hbm_ms": round(float(np.percentile(lat_d, 99)), 4),
-        "p50_latency_c3_ms": round(float(np.percentile(lat_c3, 50)), 4),
-        "p99_latency_c3_ms": round(float(np.percentile(lat_c3, 99)), 4),
+        "p50_latency_hbm_ms": pct(lat_d, 50, args.latency_frames > 0),
+        "p99_latency_hbm_ms": pct(lat_d, 99, args.latency_frames > 0),
+        "p50_latency_c3_ms": pct(lat_c3, 50, args.c3_latency_iters > 0),
+        "p99_latency_c3_ms": pct(lat_c3, 99, args.c3_latency_iters > 0),
         "latency_c3_note": "config C3: one batch of 4 camera frames (pageable host YUYV) -> detections + poses",
         "host_ingest": host_ingest,
         "detections_per_frame": round(ndet / total_frames, 3),

@@ -297,11 +297,10 @@ def test_camera_config_records(nodelib, tmp_path):
         assert nodelib.at_node_load_camera_config(str(cfg).encode(), serial, w, h, fr, loc, 64) == -1
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/vision_config_data/data"), reason="reference absent")
-def test_camera_config_of_the_reference_system_config(nodelib):
-    """The deployed records (src/vision_config_data/data/system_config.json:2-50):
-    1920x1080, 800x600 and 1280x800 cameras."""
-    path = b"/root/reference/src/vision_config_data/data/system_config.json"
+def test_camera_config_of_the_reference_system_config(nodelib, golden_dir):
+    """The deployed records (src/vision_config_data/data/system_config.json:2-50, kept
+    as tests/golden/system_config.json): 1920x1080, 800x600 and 1280x800 cameras."""
+    path = os.path.join(golden_dir, "system_config.json").encode()
     w, h, fr = C.c_int(), C.c_int(), C.c_int()
     loc = C.create_string_buffer(64)
     want = {b"HBVCAM": (1920, 1080, b"center_front"), b"12": (800, 600, b"left_front"),

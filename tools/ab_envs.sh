@@ -10,7 +10,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   ORDER=$ENVS
   if [ $((r % 2)) = 0 ]; then ORDER=$REV; fi
   for ev in $ORDER; do
-    env AT_HIP_LIB=${AT_HIP_LIB:-ros_vision_amd/ab/libat_hip_exp.so} $ev timeout -k 10 150 python3 bench.py --steps ${STEPS:-100} --warmup 5 --no-cpu-baseline \
+    env AT_HIP_LIB=${AT_HIP_LIB:-ros_vision_amd/ab/libat_hip_exp.so} $ev timeout -k 10 150 python3 bench.py --full --steps ${STEPS:-100} --warmup 5 --no-cpu-baseline \
       --latency-frames 0 --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0 --no-kernel-timer --pool 128 \
       2>>$OUT/err.txt | python3 -c "
 import json,sys; j=json.load(sys.stdin)

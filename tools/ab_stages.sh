@@ -9,7 +9,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   ORDER=$LIBS
   if [ $((r % 2)) = 0 ]; then ORDER=$REV; fi  # even rounds backwards: no position bias
   for lib in $ORDER; do
-    AT_HIP_LIB=$lib timeout -k 10 150 python3 bench.py --steps ${STEPS:-100} --warmup 5 --no-cpu-baseline \
+    AT_HIP_LIB=$lib timeout -k 10 150 python3 bench.py --full --steps ${STEPS:-100} --warmup 5 --no-cpu-baseline \
       --latency-frames ${LATFRAMES:-0} --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0 --no-kernel-timer --pool 128 \
       2>>$OUT/err.txt | python3 -c "
 import json,sys; j=json.load(sys.stdin)

@@ -10,7 +10,7 @@ python3 tools/gap_report.py $O/lat_trace/run_kernel_trace.csv > $O/lat_gaps.txt 
 bash tools/profile_round.sh $TAG > /dev/null || exit 1
 # the north-star topology at world size 1 (launcher first, one rank) beside the same
 # local loop, and the 1920x1080 geometry
-LEG="--no-cpu-baseline --latency-frames 0 --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0"
+LEG="--full --no-cpu-baseline --latency-frames 0 --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0"
 timeout -k 10 240 python bench.py $LEG > $O/bench_local_n1.json 2> $O/local.err || exit 1
 timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --ingest scatter $LEG > $O/bench_scatter_n1.json 2> $O/scatter.err || exit 1
-timeout -k 10 240 python bench.py --width 1920 --height 1080 --tags 24 --no-cpu-baseline --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0 > $O/bench_1080p.json 2> $O/bench_1080p.err || exit 1
+timeout -k 10 240 python bench.py --full --width 1920 --height 1080 --tags 24 --no-cpu-baseline --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0 > $O/bench_1080p.json 2> $O/bench_1080p.err || exit 1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU call collecting this round's profiles (MI355X_MICROARCH.md HBM/rocprofv3):
-#   1. the plain bench line (bench.json)
+#   1. the bench line with every leg, `bench.py --full` (bench.json)
 #   2. rocprofv3 --kernel-trace --stats of `bench.py --isolated-only` (every launch
 #      serialized: each kernel's rocprof average is its isolated duration) and
 #      tools/roofline_check.py: the line's roofline frac recomputed from it
@@ -22,7 +22,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 ONLY="--latency-frames 0 --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0"
 SHORT="$ROOT/bench.py --no-cpu-baseline --no-stage-profile --batch $BATCH --steps 4 --warmup 1 $ONLY --isolated-batches 0"
-timeout -k 10 400 python3 bench.py --batch $BATCH > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 400 python3 bench.py --full --batch $BATCH >"$OUT/bench.json" 2> "$OUT/bench.err"
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_iso" -o run -- \
   python3 $ROOT/bench.py --isolated-only --batch $BATCH > "$OUT/iso_traced.json" 2> "$OUT/iso_traced.err"

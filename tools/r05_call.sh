@@ -18,7 +18,7 @@ if [ -n "${GPU_TESTS:-}" ]; then
   case $rc in 0|1) ;; *) exit $rc;; esac
 fi
 if [ -n "${BENCH:-}" ]; then
-  timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || exit 1
+  timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 fi
 if [ -n "${TIMER_AB:-}" ]; then  # the timed region with and without the live kernel timer, interleaved
   LEG="--no-cpu-baseline --latency-frames 0 --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0 --no-stage-profile --isolated-batches 0"

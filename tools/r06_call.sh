@@ -27,7 +27,7 @@ if [ -n "${GPU_TESTS:-}" ]; then
   rc=$?; echo "tests rc=$rc" >> $O/rc.txt; fatal $rc
 fi
 if [ -n "${BENCH:-}" ]; then
-  timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || exit 1
+  timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 fi
 ablate() {  # $1 = output file, rest = bench geometry options
   out=$1; shift
@@ -42,7 +42,7 @@ if [ -n "${ABL:-}" ]; then ablate $O/ablation_720p.txt; fi
 if [ -n "${ABL1080:-}" ]; then ablate $O/ablation_1080p.txt --width 1920 --height 1080 --tags 24; fi
 if [ -n "${P1080:-}" ]; then
   G="--width 1920 --height 1080 --tags 24"
-  timeout -k 10 400 python bench.py $G --steps 100 --no-cpu-baseline --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0 \
+  timeout -k 10 400 python bench.py --full $G --steps 100 --no-cpu-baseline --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0 \
     --latency-frames 300 > $O/bench_1080p.json 2> $O/bench_1080p.err || exit 1
   SHORT="$R/bench.py $G --no-cpu-baseline --no-stage-profile --steps 4 --warmup 1 --latency-frames 0 --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0 --isolated-batches 0"
   (cd /tmp && timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/$O/pmc1080_fetch -o run -- python3 $SHORT > /dev/null 2> $R/$O/pmc1080_fetch.err) || exit 1
@@ -52,7 +52,7 @@ fi
 if [ -n "${BSTOPS:-}" ]; then  # blob kernels cut after phase N (AT_DIAG_BLOB_STOP): serialized stage times
   for r in 1 2; do for st in $BSTOPS; do
     echo -n "round=$r blob_stop=$st " >> $O/blob_stops.txt
-    AT_HIP_LIB=$EXP AT_DIAG_BLOB_STOP=$st timeout -k 10 200 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --latency-frames 0 \
+    AT_HIP_LIB=$EXP AT_DIAG_BLOB_STOP=$st timeout -k 10 200 python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --latency-frames 0 \
       --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0 --no-kernel-timer 2>>$O/err.txt | python3 -c "
 import json,sys; j=json.load(sys.stdin); s=j['stage_ms_per_batch']; print(j['value'], 'k_blob_small=%.4f k_blob=%.4f k_decode=%.4f' % (s['k_blob_small'], s['k_blob'], s['k_decode']))" >> $O/blob_stops.txt || exit 1
   done; done
@@ -60,7 +60,7 @@ fi
 if [ -n "${LATLIBS:-}" ]; then  # B = 1 latency of each library, interleaved rounds
   for r in 1 2 3; do for lib in $LATLIBS; do
     echo -n "round=$r lib=$lib " >> $O/lat.txt
-    AT_HIP_LIB=$lib timeout -k 10 200 python3 bench.py --steps 3 --warmup 2 --latency-frames ${LATN:-2000} --no-cpu-baseline --no-stage-profile \
+    AT_HIP_LIB=$lib timeout -k 10 200 python3 bench.py --full --steps 3 --warmup 2 --latency-frames ${LATN:-2000} --no-cpu-baseline --no-stage-profile \
       --no-kernel-timer --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0 --isolated-batches 0 2>>$O/err.txt | python3 -c "
 import json,sys; j=json.load(sys.stdin); print('p50 %.4f p99 %.4f' % (j['p50_latency_hbm_ms'], j['p99_latency_hbm_ms']))" >> $O/lat.txt || exit 1
   done; done
@@ -70,7 +70,7 @@ if [ -n "${ENVS:-}" ]; then TAG=$TAG bash tools/ab_envs.sh > /dev/null || exit 1
 if [ -n "${LIBS1080:-}" ]; then
   for r in 1 2; do for lib in $LIBS1080; do
     echo -n "round=$r lib=$lib " >> $O/ab1080.txt
-    AT_HIP_LIB=$lib timeout -k 10 200 python bench.py --width 1920 --height 1080 --tags 24 --steps ${STEPS1080:-60} --no-cpu-baseline --latency-frames 0 \
+    AT_HIP_LIB=$lib timeout -k 10 200 python bench.py --full --width 1920 --height 1080 --tags 24 --steps ${STEPS1080:-60} --no-cpu-baseline --latency-frames 0 \
       --host-ingest-steps 0 --c3-latency-iters 0 --node-path-calls 0 --no-kernel-timer --isolated-batches 0 2>>$O/err.txt | python3 -c "
 import json,sys; j=json.load(sys.stdin); print(j['value'], j['detections_per_frame'], ' '.join('%s=%.4f' % kv for kv in j['stage_ms_per_batch'].items()))" >> $O/ab1080.txt || exit 1
   done; done
