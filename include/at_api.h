@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define AT_ABI_VERSION 5
+#define AT_ABI_VERSION 6
 
 enum {
   AT_OK = 0,
@@ -31,7 +31,8 @@ enum {
   AT_E_HIP = -2,        /* HIP runtime error (no device, launch failure) */
   AT_E_CAPACITY = -3,   /* frame exceeded a fixed capacity (see at_frame_status) */
   AT_E_FAMILY = -4,     /* unknown tag family */
-  AT_E_NOMEM = -5
+  AT_E_NOMEM = -5,
+  AT_E_UNSUPPORTED = -6 /* a JPEG stream the MJPG path does not decode (see at_enqueue_mjpg) */
 };
 
 typedef struct at_detector at_detector; /* opaque: device buffers + hipStream_t */
@@ -115,6 +116,50 @@ int at_collect(at_detector *d, at_detection *out, int cap_per_frame, int *n_per_
  * of one batch overlap the kernels of another.  The frames must stay untouched
  * until at_collect. */
 int at_enqueue_host(at_detector *d, const uint8_t *const *frames, int nframes, at_pixfmt fmt);
+
+/* MJPG camera frames (what every camera of the deployed configuration delivers).
+ * Each frame is one baseline sequential 8-bit Huffman JPEG (SOF0) of the detector's
+ * size: 3 components 4:4:4, 4:2:2 or 4:2:0 in one interleaved scan, or 1 component;
+ * DRI / RSTn restarts; APPn (the AVI1 APP0 of UVC cameras) and COM are skipped; a
+ * stream without DHT segments is decoded with the standard Annex K tables.  Only luma
+ * is decoded: the host does the Huffman decode and sends the quantised luma
+ * coefficients (at most 2 B per pixel, typically well under 1), the GPU dequantises,
+ * runs the inverse DCT and writes the GRAY8 plane the detection then reads.  The plane
+ * equals libjpeg's integer "slow" IDCT luma bit for bit.
+ *
+ * at_enqueue_mjpg first parses and entropy-decodes every frame on the host.  If one
+ * fails, nothing is enqueued, the detector (a pending batch included) is as before,
+ * *bad_frame (may be NULL) is its index and the code is returned: AT_E_UNSUPPORTED for
+ * progressive, arithmetic-coded, 12-bit, 4-component or otherwise sampled streams,
+ * AT_E_INVALID for malformed or truncated ones and for a size other than the
+ * detector's.  Otherwise it continues like at_enqueue_host with GRAY8 frames;
+ * at_collect, at_poses, at_detections, at_frame_status and at_debug_copy follow as
+ * usual (AT_STAGE_GRAY with the taps on is the decoded plane).  at_annotate_staged
+ * after an MJPG batch is AT_E_INVALID: there is no chroma on the device.
+ * The host decode waits for nothing, so called while the batch before is still running
+ * it overlaps that batch (two staging sets); like every enqueue it then waits for a
+ * batch not yet collected before it reuses the result buffers.
+ * The jpgs need to stay valid only until the call returns. */
+int at_enqueue_mjpg(at_detector *d, const uint8_t *const *jpgs, const size_t *lens, int nframes, int *bad_frame);
+int at_detect_mjpg(at_detector *d, const uint8_t *jpg, size_t len, at_detection *out, int cap, int *n);
+int at_detect_mjpg_batch(at_detector *d, const uint8_t *const *jpgs, const size_t *lens, int nframes,
+                         at_detection *out, int cap_per_frame, int *n_per_frame, int *bad_frame);
+/* Host threads that decode the frames of one MJPG batch (default 1; clamped to 1..16). */
+int at_mjpg_set_threads(at_detector *d, int n);
+/* The last enqueued MJPG batch: [0] compressed bytes in, [1] bytes sent to the device,
+ * [2] frames sent in the dense encoding, [3] host parse + decode time, microseconds,
+ * [4] k_mjpg_idct's time in nanoseconds (HIP events; measured while at_set_profiling
+ * is on and known once the batch is collected, 0 otherwise).
+ * Returns the number of entries written. */
+int at_mjpg_stats(at_detector *d, uint64_t *out, int cap);
+/* Host only, no device needed: the full luma decode of one such JPEG (any size up to
+ * 2^26 pixels) with the same integer IDCT the kernel runs -- the CPU reference of the
+ * MJPG path.  *w / *h (may be NULL) receive the picture size; gray == NULL parses the
+ * frame header only.  at_mjpg_stream_mode_host tells how the frame would travel to a
+ * want_w x want_h detector (0, 0: any size): 0 sparse, 1 dense, < 0 the error
+ * at_enqueue_mjpg would return; *stream_bytes (may be NULL) its size on the link. */
+int at_mjpg_decode_gray_host(const uint8_t *jpg, size_t len, uint8_t *gray, size_t cap, int *w, int *h);
+int at_mjpg_stream_mode_host(const uint8_t *jpg, size_t len, int want_w, int want_h, size_t *stream_bytes);
 
 /* Stream ordering without a host wait: the detector's next enqueued batch starts
  * only after everything queued so far on `stream` (a hipStream_t of the same

@@ -1,13 +1,15 @@
 // at_mock_node.cpp -- the node core driven from raw frame files (no ROS 2 here).
 //
 // Stands in for the subscription: every frame of --frames (back-to-back raw
-// bgr8 / yuyv / gray frames) is handed to DetectorCore::process exactly as
+// bgr8 / yuyv / gray frames, or -- a .jpg / .mjpg file, or --format mjpg -- JPEG
+// frames back to back as a camera's MJPG stream delivers them, handed to
+// DetectorCore::process_compressed) is handed to DetectorCore::process exactly as
 // ApriltagsDetector::imageCallback hands its cv_bridge image to the detector
 // (apriltags_cuda_detector.cu:382-557).  Publishers print one JSON line per
 // frame; --proto-out / --image-out write the ApriltagListProto bytes and the
 // outlined bgr8 image of the last frame.
 //
-// usage: at_mock_node --camera-serial S --format bgr8|yuyv|gray --frames F [--count N]
+// usage: at_mock_node --camera-serial S --format bgr8|yuyv|gray|mjpg --frames F [--count N]
 //        [--vision-config-dir D] [--pin-to-core C --priority P]
 //        [--measurement-csv PATH] [--proto-out P] [--image-out I] [--device K] [--time N]
 //   As the reference node (apriltags_cuda_detector.cu:137-193): the frame size, the
@@ -46,6 +48,35 @@ std::string msgs_json(const std::vector<at_node::TagDetectionMsg>& v) {
 }
 void on_robot(void* ctx, const std::vector<at_node::TagDetectionMsg>& v) { ((Sink*)ctx)->robot = msgs_json(v); }
 void on_camera(void* ctx, const std::vector<at_node::TagDetectionMsg>& v) { ((Sink*)ctx)->camera = msgs_json(v); }
+
+bool ends_with(const std::string& s, const char* suffix) {
+  const size_t n = std::strlen(suffix);
+  return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
+}
+struct Span {
+  size_t off, len;
+};
+// JPEG frames back to back: each runs from an SOI (FF D8 FF) to the EOI (FF D9) that
+// the next SOI or the end of the file follows
+std::vector<Span> split_mjpg(const std::vector<uint8_t>& d) {
+  std::vector<Span> v;
+  size_t i = 0;
+  const size_t n = d.size();
+  while (i + 3 <= n) {
+    if (!(d[i] == 0xff && d[i + 1] == 0xd8 && d[i + 2] == 0xff)) {
+      ++i;
+      continue;
+    }
+    size_t e = i + 2;
+    for (; e + 2 <= n; ++e)
+      if (d[e] == 0xff && d[e + 1] == 0xd9 && (e + 2 == n || (e + 4 <= n && d[e + 2] == 0xff && d[e + 3] == 0xd8)))
+        break;
+    const size_t end = e + 2 <= n ? e + 2 : n;  // (no EOI: the rest of the file, the decoder judges it)
+    v.push_back({i, end - i});
+    i = end;
+  }
+  return v;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -98,15 +129,24 @@ int main(int argc, char** argv) {
   W = nc.camera.width;
   H = nc.camera.height;
   const std::string& location = nc.location;
+  if (ends_with(frames_path, ".jpg") || ends_with(frames_path, ".jpeg") || ends_with(frames_path, ".mjpg"))
+    fmt_s = "mjpg";
+  const bool mjpg = fmt_s == "mjpg";
   const at_pixfmt fmt = fmt_s == "bgr8" ? AT_FMT_BGR8 : (fmt_s == "gray" ? AT_FMT_GRAY8 : AT_FMT_YUYV);
   const size_t fb = (size_t)W * H * (fmt == AT_FMT_BGR8 ? 3 : (fmt == AT_FMT_YUYV ? 2 : 1));
   if (W <= 0 || H <= 0 || frames_path.empty()) {
-    std::fprintf(stderr, "usage: %s --camera-serial S --format bgr8|yuyv|gray --frames FILE ...\n", argv[0]);
+    std::fprintf(stderr, "usage: %s --camera-serial S --format bgr8|yuyv|gray|mjpg --frames FILE ...\n", argv[0]);
     return 2;
   }
   std::ifstream in(frames_path, std::ios::binary);
   std::vector<uint8_t> all((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
-  const int nframes = (int)(all.size() / fb);
+  std::vector<Span> spans;
+  if (mjpg) {
+    spans = split_mjpg(all);
+  } else {
+    for (size_t o = 0; o + fb <= all.size(); o += fb) spans.push_back({o, fb});
+  }
+  const int nframes = (int)spans.size();
   if (count < 0 || count > nframes) count = nframes;
   if (time_n > 0 && count <= 0) {  // the timed loop walks the frames modulo count
     std::fprintf(stderr, "%s: --time needs at least one frame (--count %d, %d frames in %s)\n", argv[0], count,
@@ -128,14 +168,18 @@ int main(int argc, char** argv) {
     core.ctx = &sink;
     at_node::FrameOutputs out;
     at_node::ImageBuffer image;
+    auto run = [&](int f, double stamp) {
+      const uint8_t* p = all.data() + spans[(size_t)f].off;
+      if (mjpg) return core.process_compressed(p, spans[(size_t)f].len, stamp, stamp, &out);
+      return core.process(p, fmt, stamp, stamp, &out, fmt == AT_FMT_BGR8 ? &image : nullptr);
+    };
     if (time_n > 0) {  // the node's per-frame path, timed
       std::vector<double> ms, det_ms;
       for (int it = -count; it < time_n; ++it) {  // (the first pass over the frames is warm-up)
         const int f = ((it % count) + count) % count;
         const double stamp = 1000.0 + 0.02 * (it + count);
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = core.process(all.data() + (size_t)f * fb, fmt, stamp, stamp, &out,
-                                    fmt == AT_FMT_BGR8 ? &image : nullptr);
+        const int rc = run(f, stamp);
         const auto t1 = std::chrono::steady_clock::now();
         if (rc != AT_OK && rc != AT_E_CAPACITY) {
           std::fprintf(stderr, "frame %d: %s\n", f, at_strerror(rc));
@@ -157,8 +201,7 @@ int main(int argc, char** argv) {
     }
     for (int f = 0; f < count; ++f) {
       const double stamp = 1000.0 + 0.02 * f;
-      const int rc = core.process(all.data() + (size_t)f * fb, fmt, stamp, stamp, &out,
-                                  fmt == AT_FMT_BGR8 ? &image : nullptr);
+      const int rc = run(f, stamp);
       if (rc != AT_OK && rc != AT_E_CAPACITY) {
         std::fprintf(stderr, "frame %d: %s\n", f, at_strerror(rc));
         return 1;

@@ -493,6 +493,17 @@ DetectorCore::~DetectorCore() {
 
 int DetectorCore::process(const uint8_t* frame, at_pixfmt fmt, double stamp_s, double receive_s, FrameOutputs* out,
                           ImageBuffer* annotate) {
+  return run(frame, 0, (int)fmt, stamp_s, receive_s, out, annotate);
+}
+
+int DetectorCore::process_compressed(const uint8_t* data, size_t len, double stamp_s, double receive_s,
+                                     FrameOutputs* out) {
+  return run(data, len, -1, stamp_s, receive_s, out, nullptr);
+}
+
+// fmt < 0: `frame` is one MJPG frame of `len` bytes (at_detect_mjpg); the tail is the same
+int DetectorCore::run(const uint8_t* frame, size_t len, int fmt, double stamp_s, double receive_s, FrameOutputs* out,
+                      ImageBuffer* annotate) {
   using clk = std::chrono::steady_clock;
   auto us = [](clk::time_point a, clk::time_point b) {
     return (long long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count();
@@ -501,7 +512,8 @@ int DetectorCore::process(const uint8_t* frame, at_pixfmt fmt, double stamp_s, d
   *out = FrameOutputs{};
   int n = 0;
   const auto det0 = clk::now();
-  int rc = at_detect(det_, frame, fmt, dets_.data(), (int)dets_.size(), &n);
+  int rc = fmt < 0 ? at_detect_mjpg(det_, frame, len, dets_.data(), (int)dets_.size(), &n)
+                   : at_detect(det_, frame, (at_pixfmt)fmt, dets_.data(), (int)dets_.size(), &n);
   const auto det1 = clk::now();
   out->status = rc;
   out->det_time_us = us(det0, det1);

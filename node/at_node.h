@@ -230,6 +230,11 @@ class DetectorCore {
   // then gets it from the drop-oldest PublisherQueue thread (depth 2, :50-52, :518).
   int process(const uint8_t* frame, at_pixfmt fmt, double stamp_s, double receive_s, FrameOutputs* out,
               ImageBuffer* annotate = nullptr);
+  // One MJPG camera frame (a sensor_msgs/CompressedImage's data: one baseline JPEG of
+  // the detector's size): at_detect_mjpg, then the same tail.  No annotated image:
+  // only luma reaches the GPU.  AT_E_UNSUPPORTED / AT_E_INVALID for a stream the
+  // library refuses (nothing is published then).
+  int process_compressed(const uint8_t* data, size_t len, double stamp_s, double receive_s, FrameOutputs* out);
 
   const Params& params() const { return params_; }
   int width() const { return width_; }
@@ -252,6 +257,8 @@ class DetectorCore {
 
  private:
   void init(const at_camera& cam, int device);
+  int run(const uint8_t* frame, size_t len, int fmt, double stamp_s, double receive_s, FrameOutputs* out,
+          ImageBuffer* annotate);
   int width_, height_;
   Params params_;
   struct StampedImage {

@@ -16,10 +16,12 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/at_api.h"
 #include "at_common.h"
+#include "at_mjpg.h"
 
 namespace at {
 hipError_t launch_tap_sizes(const uint8_t* thr, const uint32_t* par, const uint32_t* size, uint32_t* out, int Wd,
@@ -27,6 +29,8 @@ hipError_t launch_tap_sizes(const uint8_t* thr, const uint32_t* par, const uint3
 hipError_t launch_tap_labels(const uint8_t* thr, const uint32_t* par, uint32_t* out, int Wd, int Hd, hipStream_t st);
 hipError_t launch_gp_preprocess(const uint8_t* src, int w, int h, float* out, int ow, int oh, int c, hipStream_t st);
 hipError_t launch_draw(const DrawPrim* prims, int n, uint32_t* last, uint8_t* bgr, int W, int H, hipStream_t st);
+hipError_t launch_mjpg_idct(const uint8_t* coef, size_t slot, uint8_t* out, size_t out_stride, int W, int H,
+                            int nframes, hipStream_t st);
 hipError_t prepare_kernels(const Geom& g);
 hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, int B, int fmt, int nblobwg,
                            hipStream_t st, hipEvent_t* ev, hipStream_t st2, hipEvent_t fork, hipEvent_t join,
@@ -110,6 +114,9 @@ static FamilyDesc family_desc(const FamilyInfo& f) {
 
 using namespace at;
 
+static_assert(kMjpgInvalid == AT_E_INVALID && kMjpgUnsupported == AT_E_UNSUPPORTED && kMjpgOk == AT_OK,
+              "at_mjpg.h carries the ABI's codes");
+
 // control block layout (u32 words, zeroed every batch): per-frame arrays of B
 // words, then scalars
 enum { kCtlNpts, kCtlNpairs, kCtlNdets, kCtlNquads, kCtlStatus, kCtlNpent, kCtlNqcand, kCtlCclOvf, kCtlNlr,
@@ -179,6 +186,22 @@ struct at_detector {
   DrawPrim* d_prims;
   size_t prims_cap;
   uint32_t* d_last;
+  // MJPG input (at_enqueue_mjpg), allocated on the first MJPG call for max_batch frames:
+  // coefficient streams [B][mj_slot] in HBM and two page-locked staging sets of the same
+  // shape, used in turn -- the host decodes a batch into one set while the copy of the
+  // batch before may still be reading the other
+  uint8_t* mj_host[2];
+  uint8_t* d_mj;
+  size_t mj_slot;
+  int mj_cur;               // staging set of the last enqueued MJPG batch
+  int mj_threads;           // host decode threads per batch (at_mjpg_set_threads)
+  std::vector<at::MjpgDecoder> mj_dec;  // one decoder (with its scratch lists) per thread
+  std::vector<int> mj_rc;
+  std::vector<size_t> mj_bytes;   // per frame: bytes of its coefficient stream
+  std::vector<uint8_t> mj_dense;  // ... and whether it took the dense encoding
+  uint64_t mj_stats[5];     // last MJPG batch: compressed bytes, bytes sent, dense frames, decode us, kernel ns
+  hipEvent_t ev_mj[2];      // around k_mjpg_idct while stage profiling is on (created on first use)
+  int mj_timed;             // the pending batch recorded them
 };
 
 // Experiment and diagnostic knobs (stage cut-offs, grid / tile overrides, phase
@@ -224,6 +247,7 @@ const char* at_strerror(int code) {
     case AT_E_CAPACITY: return "frame exceeded a fixed capacity";
     case AT_E_FAMILY: return "unknown tag family";
     case AT_E_NOMEM: return "out of memory";
+    case AT_E_UNSUPPORTED: return "unsupported JPEG stream (not baseline 8-bit 4:4:4 / 4:2:2 / 4:2:0 / gray)";
     default: return "unknown error";
   }
 }
@@ -278,6 +302,10 @@ void at_destroy(at_detector* d) {
   if (d->h_dets) (void)hipHostFree(d->h_dets);
   if (d->d_prims) (void)hipFree(d->d_prims);
   if (d->d_last) (void)hipFree(d->d_last);
+  for (uint8_t* p : d->mj_host)
+    if (p) (void)hipHostFree(p);
+  for (hipEvent_t e : d->ev_mj)
+    if (e) (void)hipEventDestroy(e);
   if (d->ev_done) (void)hipEventDestroy(d->ev_done);
   if (d->ev_ext) (void)hipEventDestroy(d->ev_ext);
   for (int i = 0; i <= kNumStages; i++)
@@ -310,6 +338,7 @@ int at_create(const at_config* cfg, const at_camera* cam, at_detector** out) {
   d->cam = *cam;
   d->device = cfg->device;
   d->B = cfg->max_batch;
+  d->mj_threads = 1;
   Geom& g = d->g;
   g.W = W; g.H = H; g.Wd = W / 2; g.Hd = H / 2;
   g.TW = g.Wd / 4; g.TH = g.Hd / 4;
@@ -750,6 +779,12 @@ static int collect(at_detector* d, at_detection* out, int cap_per_frame, int* n_
     }
     d->stage_batches++;
   }
+  if (d->mj_timed) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, d->ev_mj[0], d->ev_mj[1]));
+    d->mj_stats[4] = (uint64_t)((double)ms * 1e6);
+    d->mj_timed = 0;
+  }
   if (d->kt.stage >= 0) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, d->kt.t0, d->kt.t1));
@@ -850,6 +885,138 @@ int at_detect(at_detector* d, const uint8_t* frame, at_pixfmt fmt, at_detection*
   const uint8_t* frames[1] = {frame};
   int nn = 0;
   const int rc = at_detect_batch(d, frames, 1, fmt, out, cap, &nn);
+  if (n) *n = nn;
+  return rc;
+}
+
+// ---- MJPG input ---------------------------------------------------------------
+// The host parses and entropy-decodes every frame of the batch (at_mjpg.cpp) straight
+// into page-locked staging, before anything is waited for or enqueued: a batch still
+// running on the GPU is not in the way (its copy read the other staging set), and a bad
+// frame leaves the detector as it was.  Then the coefficient streams go to the device,
+// k_mjpg_idct writes the GRAY8 planes into the frames' staging slots, and the batch
+// continues as host-fed GRAY8 frames (the captured launch sequence is the GRAY8 one).
+static int mjpg_prepare(at_detector* d) {
+  if (d->d_mj) return AT_OK;
+  const size_t nb = (size_t)(d->g.W / 8) * (d->g.H / 8);
+  const size_t slot = ((size_t)kMjpgHdrBytes + 128 * nb + 255) & ~(size_t)255;
+  const size_t total = slot * (size_t)d->B;
+  uint8_t* h[2] = {nullptr, nullptr};
+  void* dev = nullptr;
+  if (hipHostMalloc((void**)&h[0], total, hipHostMallocDefault) != hipSuccess ||
+      hipHostMalloc((void**)&h[1], total, hipHostMallocDefault) != hipSuccess ||
+      hipMalloc(&dev, total) != hipSuccess) {
+    if (h[0]) (void)hipHostFree(h[0]);
+    if (h[1]) (void)hipHostFree(h[1]);
+    return AT_E_NOMEM;
+  }
+  d->allocs.push_back(dev);
+  d->d_mj = (uint8_t*)dev;
+  d->mj_host[0] = h[0];
+  d->mj_host[1] = h[1];
+  d->mj_slot = slot;
+  d->mj_cur = 1;
+  d->mj_dec.resize(16);  // at_mjpg_set_threads' upper bound
+  d->mj_rc.assign((size_t)d->B, 0);
+  d->mj_bytes.assign((size_t)d->B, 0);
+  d->mj_dense.assign((size_t)d->B, 0);
+  return AT_OK;
+}
+
+int at_mjpg_set_threads(at_detector* d, int n) {
+  if (!d) return AT_E_INVALID;
+  d->mj_threads = std::max(1, std::min(16, n));
+  return AT_OK;
+}
+
+int at_mjpg_stats(at_detector* d, uint64_t* out, int cap) {
+  if (!d || !out || cap < 1) return AT_E_INVALID;
+  const int n = std::min(cap, 5);
+  for (int i = 0; i < n; i++) out[i] = d->mj_stats[i];
+  return n;
+}
+
+int at_enqueue_mjpg(at_detector* d, const uint8_t* const* jpgs, const size_t* lens, int nframes, int* bad_frame) {
+  if (bad_frame) *bad_frame = -1;
+  if (!d || !jpgs || !lens || nframes < 1 || nframes > d->B) return AT_E_INVALID;
+  for (int f = 0; f < nframes; f++)
+    if (!jpgs[f]) {
+      if (bad_frame) *bad_frame = f;
+      return AT_E_INVALID;
+    }
+  HIPCHK(hipSetDevice(d->device));
+  const int prc = mjpg_prepare(d);
+  if (prc != AT_OK) return prc;
+  const int set = d->mj_cur ^ 1;
+  uint8_t* stage = d->mj_host[set];
+  const double t0 = now_us();
+  const int nthr = std::min(d->mj_threads, nframes);
+  auto work = [&](int t) {
+    at::MjpgDecoder& dec = d->mj_dec[(size_t)t];
+    for (int f = t; f < nframes; f += nthr) {
+      int rc = dec.decode(jpgs[f], lens[f], d->g.W, d->g.H);
+      if (rc == AT_OK) {
+        d->mj_bytes[(size_t)f] = dec.packed_bytes();
+        rc = dec.pack(stage + (size_t)f * d->mj_slot, d->mj_slot);
+        d->mj_dense[(size_t)f] = dec.dense() ? 1 : 0;
+      }
+      d->mj_rc[(size_t)f] = rc;
+    }
+  };
+  if (nthr > 1) {
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nthr; t++) pool.emplace_back(work, t);
+    work(0);
+    for (auto& th : pool) th.join();
+  } else {
+    work(0);
+  }
+  const double t1 = now_us();
+  for (int f = 0; f < nframes; f++)
+    if (d->mj_rc[(size_t)f] != AT_OK) {
+      if (bad_frame) *bad_frame = f;
+      return d->mj_rc[(size_t)f];  // nothing enqueued, the staging set in use untouched
+    }
+  if (d->pending) HIPCHK(hipEventSynchronize(d->ev_done));  // the frame table and result buffers are reused
+  uint64_t st[5] = {0, 0, 0, (uint64_t)(t1 - t0), 0};
+  for (int f = 0; f < nframes; f++) {
+    const size_t nbytes = d->mj_bytes[(size_t)f];
+    st[0] += lens[f];
+    st[1] += nbytes;
+    st[2] += d->mj_dense[(size_t)f];
+    HIPCHK(hipMemcpyAsync(d->d_mj + (size_t)f * d->mj_slot, stage + (size_t)f * d->mj_slot, nbytes,
+                          hipMemcpyHostToDevice, d->st));
+    d->h_ftab[f] = d->d_in + (size_t)f * d->in_stride;
+  }
+  d->mj_cur = set;
+  const bool timed = d->profiling != 0;
+  if (timed) {
+    for (hipEvent_t& e : d->ev_mj)
+      if (!e) HIPCHK(hipEventCreateWithFlags(&e, kTimingEventFlags));
+    HIPCHK(hipEventRecord(d->ev_mj[0], d->st));
+  }
+  HIPCHK(launch_mjpg_idct(d->d_mj, d->mj_slot, d->d_in, d->in_stride, d->g.W, d->g.H, nframes, d->st));
+  if (timed) HIPCHK(hipEventRecord(d->ev_mj[1], d->st));
+  d->mj_timed = timed;
+  const int rc = enqueue(d, nframes, AT_FMT_GRAY8);
+  if (rc) return rc;
+  d->last_staged = 1;
+  memcpy(d->mj_stats, st, sizeof(st));
+  return AT_OK;
+}
+
+int at_detect_mjpg_batch(at_detector* d, const uint8_t* const* jpgs, const size_t* lens, int nframes,
+                         at_detection* out, int cap_per_frame, int* n_per_frame, int* bad_frame) {
+  const int rc = at_enqueue_mjpg(d, jpgs, lens, nframes, bad_frame);
+  if (rc) return rc;
+  return collect(d, out, cap_per_frame, n_per_frame);
+}
+
+int at_detect_mjpg(at_detector* d, const uint8_t* jpg, size_t len, at_detection* out, int cap, int* n) {
+  const uint8_t* jpgs[1] = {jpg};
+  const size_t lens[1] = {len};
+  int nn = 0;
+  const int rc = at_detect_mjpg_batch(d, jpgs, lens, 1, out, cap, &nn, nullptr);
   if (n) *n = nn;
   return rc;
 }

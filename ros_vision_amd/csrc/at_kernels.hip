@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "at_common.h"
+#include "at_mjpg.h"
 #include "at_pose.h"
 
 
@@ -5381,6 +5382,115 @@ hipError_t launch_draw(const DrawPrim* prims, int n, uint32_t* last, uint8_t* bg
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_draw<false>, dim3(n), dim3(256), 0, st, prims, last, bgr, W, H);
   hipLaunchKernelGGL(k_draw<true>, dim3(n), dim3(256), 0, st, prims, last, bgr, W, H);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// MJPG input: the arithmetic half of a baseline JPEG luma decode.  The host
+// (at_mjpg.cpp) has done the serial half -- Huffman decode, DC prediction, restart
+// handling -- and sends per frame the luma quantisation table and the quantised
+// coefficients of the W/8 x H/8 visible blocks, sparse (offset table + tokens) or
+// dense (at_mjpg.h has the layout).  This kernel dequantises, runs libjpeg's
+// integer "slow" inverse DCT (mjpg_idct_1d: column pass descaled by 11 bits, row
+// pass by 18, + 128, clamped) and writes the GRAY8 plane of every frame of the
+// batch into its staging slot, where the launch sequence reads a GRAY8 frame.
+//
+// One workgroup of 256 threads takes 32 consecutive blocks, 8 lanes per block, a
+// wave 8 blocks:
+//   load    dense: lane j of a block reads coefficients 8j..8j+7 (one 16-byte load,
+//           consecutive lanes consecutive addresses); sparse: the 8 lanes stride
+//           over the block's tokens.  Dequantised values go to LDS as int32.
+//   columns lane c runs the 1-D pass down column c of its block (ds_read_b32 /
+//           ds_write_b32 at word 72 * block + 8 * r + c: the 32 lanes of a half wave
+//           cover 4 blocks x 8 columns = banks 8 * block + c of 32, no conflict;
+//           72 = 64 + 8 words per block is that padding).
+//   rows    lane (r, block) = (lane / 8, lane % 8) of the wave runs the 1-D pass
+//           along row r of its block (two 16-byte LDS reads), packs the 8 pixels
+//           and stores them as one 8-byte word: the 8 lanes of one r write 64
+//           consecutive bytes of an image row when the 8 blocks are row neighbours.
+// Integers only (no float, nothing -ffp-contract could touch).
+// ---------------------------------------------------------------------------
+constexpr int kMjpgBlocksPerWg = 32, kMjpgLdsStride = 72;
+__constant__ uint8_t c_mjpg_zigzag[64] = AT_MJPG_ZIGZAG;
+
+__global__ __launch_bounds__(256) void k_mjpg_idct(const uint8_t* __restrict__ coef, size_t slot,
+                                                   uint8_t* __restrict__ out, size_t out_stride, int W, int bw,
+                                                   uint32_t nb) {
+  __shared__ __attribute__((aligned(16))) int32_t ws[kMjpgBlocksPerWg * kMjpgLdsStride];
+  const int f = blockIdx.y;
+  const uint8_t* fr = coef + (size_t)f * slot;
+  const uint16_t* q = reinterpret_cast<const uint16_t*>(fr);
+  const uint32_t mode = *reinterpret_cast<const uint32_t*>(fr + kMjpgModeOff);
+  const uint32_t ntok = *reinterpret_cast<const uint32_t*>(fr + kMjpgNtokOff);
+  const uint8_t* pay = fr + kMjpgHdrBytes;
+  const int t = threadIdx.x;
+  const uint32_t blk0 = blockIdx.x * kMjpgBlocksPerWg;
+  {
+    const int lb = t >> 3, j = t & 7;
+    const uint32_t blk = blk0 + lb;
+    int32_t* w = ws + lb * kMjpgLdsStride + 8 * j;
+    if (mode == kMjpgDense) {
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (blk < nb) v = *reinterpret_cast<const uint4*>(pay + ((size_t)blk * 64 + 8 * j) * 2);
+      const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        w[2 * k] = (int32_t)(int16_t)(u[k] & 0xffffu) * (int32_t)q[8 * j + 2 * k];
+        w[2 * k + 1] = (int32_t)(int16_t)(u[k] >> 16) * (int32_t)q[8 * j + 2 * k + 1];
+      }
+      __syncthreads();
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; k++) w[k] = 0;
+      __syncthreads();
+      if (blk < nb) {
+        const uint32_t* off = reinterpret_cast<const uint32_t*>(pay);
+        const uint32_t* tok = off + nb + 1;
+        const uint32_t end = min(off[blk + 1], ntok);
+        int32_t* wb = ws + lb * kMjpgLdsStride;
+        for (uint32_t i = off[blk] + j; i < end; i += 8) {
+          const uint32_t tk = tok[i];
+          const int nat = c_mjpg_zigzag[(tk >> 16) & 63];
+          wb[nat] = (int32_t)(int16_t)(tk & 0xffffu) * (int32_t)q[nat];
+        }
+      }
+      __syncthreads();
+    }
+    // column pass: lane j is column j of block lb
+    int32_t* col = ws + lb * kMjpgLdsStride + j;
+    int32_t v[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) v[r] = col[8 * r];
+    mjpg_idct_1d<11>(v);
+#pragma unroll
+    for (int r = 0; r < 8; r++) col[8 * r] = v[r];
+  }
+  __syncthreads();
+  {
+    // row pass: the wave's 8 blocks, lane = 8 * row + block
+    const int l = t & 63, lb = (t >> 6) * 8 + (l & 7), r = l >> 3;
+    const uint32_t blk = blk0 + lb;
+    const int4* row = reinterpret_cast<const int4*>(ws + lb * kMjpgLdsStride + 8 * r);
+    const int4 a = row[0], b4 = row[1];
+    int32_t v[8] = {a.x, a.y, a.z, a.w, b4.x, b4.y, b4.z, b4.w};
+    mjpg_idct_1d<18>(v);
+    uint2 px;
+    px.x = mjpg_pixel(v[0]) | (mjpg_pixel(v[1]) << 8) | (mjpg_pixel(v[2]) << 16) | (mjpg_pixel(v[3]) << 24);
+    px.y = mjpg_pixel(v[4]) | (mjpg_pixel(v[5]) << 8) | (mjpg_pixel(v[6]) << 16) | (mjpg_pixel(v[7]) << 24);
+    if (blk < nb) {
+      const uint32_t by = blk / (uint32_t)bw, bx = blk - by * (uint32_t)bw;
+      *reinterpret_cast<uint2*>(out + (size_t)f * out_stride + ((size_t)by * 8 + r) * W + (size_t)bx * 8) = px;
+    }
+  }
+}
+
+// coef: nframes coefficient streams `slot` bytes apart; out: nframes GRAY8 planes
+// (W x H, W % 8 == 0, H % 8 == 0) out_stride bytes apart
+hipError_t launch_mjpg_idct(const uint8_t* coef, size_t slot, uint8_t* out, size_t out_stride, int W, int H,
+                            int nframes, hipStream_t st) {
+  const uint32_t nb = (uint32_t)(W / 8) * (uint32_t)(H / 8);
+  hipLaunchKernelGGL(k_mjpg_idct, dim3((nb + kMjpgBlocksPerWg - 1) / kMjpgBlocksPerWg, nframes), dim3(256), 0, st,
+                     coef, slot, out, out_stride, W, W / 8, nb);
   return hipGetLastError();
 }
 

@@ -1,0 +1,161 @@
+// at_mjpg.h -- host JPEG front end of the MJPG input path.
+//
+// Baseline sequential 8-bit Huffman JPEG (SOF0), the format UVC cameras emit as
+// MJPG.  The serial part of the decode runs on the host: marker parsing, Huffman
+// decode of every component (an interleaved scan cannot skip the chroma bits), DC
+// prediction and restart handling.  Only the luma coefficients are kept (AprilTag
+// detection reads luma); they go to the GPU still quantised, where k_mjpg_idct
+// (at_kernels.hip) dequantises, runs the inverse DCT and writes the GRAY8 plane.
+//
+// Plain C++17, no HIP include: compiles alone with the host compiler (the
+// sanitized stand-alone check tests/mjpg_host_check.cpp builds it that way).
+//
+// Coefficient stream of one frame (what the host writes and the kernel reads):
+//   header, kMjpgHdrBytes:
+//     u16 q[64]     luma quantisation table, natural (row-major) order
+//     u32 mode      kMjpgSparse / kMjpgDense
+//     u32 ntokens   sparse: number of tokens
+//     u32 nblocks   (W/8) * (H/8)
+//   payload, sparse:  u32 off[nblocks + 1], then u32 token[ntokens]; block b owns
+//                     token[off[b] .. off[b+1]); a token is (zig-zag position << 16) |
+//                     (u16)(i16 quantised value); only non-zero coefficients appear
+//   payload, dense:   i16 coef[nblocks][64], natural order
+// Blocks are in raster order of the W/8 x H/8 grid: the blocks an MCU grid pads
+// beyond the picture (4:2:0 at 1080 rows: 1088) are decoded for their DC
+// prediction and dropped here, so the stream holds exactly the visible blocks.
+// Dense is chosen whenever sparse would not be smaller, so the payload never
+// exceeds 128 B per block (2 B per pixel) and no frame can fail for size.
+#ifndef AT_MJPG_H_
+#define AT_MJPG_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#if defined(__HIP__)  // compiled as HIP: the kernel calls the IDCT pass too
+#define AT_MJPG_HD __attribute__((host)) __attribute__((device)) inline __attribute__((always_inline))
+#else
+#define AT_MJPG_HD inline
+#endif
+
+namespace at {
+
+constexpr int kMjpgHdrBytes = 256;
+constexpr uint32_t kMjpgSparse = 0, kMjpgDense = 1;
+constexpr int kMjpgModeOff = 128, kMjpgNtokOff = 132, kMjpgNblkOff = 136;
+
+// error codes of include/at_api.h (this header stands alone)
+constexpr int kMjpgOk = 0, kMjpgInvalid = -1, kMjpgUnsupported = -6;
+
+// zig-zag position -> natural index (ITU-T T.81 figure 5)
+#define AT_MJPG_ZIGZAG                                                                            \
+  {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,       \
+   41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,       \
+   30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}
+
+// One 1-D pass of libjpeg's integer "slow" inverse DCT (jidctint: 13-bit constants,
+// 2 pass bits), on 8 values in place.  SHIFT is the descale: 11 for the column
+// pass (CONST_BITS - PASS1_BITS), 18 for the row pass (CONST_BITS + PASS1_BITS + 3).
+// Integers only; the sums wrap in uint32_t, which is the same bit pattern as int32
+// arithmetic on every valid stream and defined behaviour on a corrupt one.
+template <int SHIFT>
+AT_MJPG_HD void mjpg_idct_1d(int32_t (&v)[8]) {
+  typedef uint32_t U;
+  const U i0 = (U)v[0], i1 = (U)v[1], i2 = (U)v[2], i3 = (U)v[3], i4 = (U)v[4], i5 = (U)v[5], i6 = (U)v[6],
+          i7 = (U)v[7];
+  // even part
+  U z1 = (i2 + i6) * 4433u;         // FIX(0.541196100)
+  U tmp2 = z1 - i6 * 15137u;        // FIX(1.847759065)
+  U tmp3 = z1 + i2 * 6270u;         // FIX(0.765366865)
+  U tmp0 = (i0 + i4) << 13;
+  U tmp1 = (i0 - i4) << 13;
+  const U tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  // odd part
+  tmp0 = i7; tmp1 = i5; tmp2 = i3; tmp3 = i1;
+  z1 = tmp0 + tmp3;
+  U z2 = tmp1 + tmp2, z3 = tmp0 + tmp2, z4 = tmp1 + tmp3;
+  const U z5 = (z3 + z4) * 9633u;   // FIX(1.175875602)
+  tmp0 *= 2446u;                    // FIX(0.298631336)
+  tmp1 *= 16819u;                   // FIX(2.053119869)
+  tmp2 *= 25172u;                   // FIX(3.072711026)
+  tmp3 *= 12299u;                   // FIX(1.501321110)
+  z1 = 0u - z1 * 7373u;             // -FIX(0.899976223)
+  z2 = 0u - z2 * 20995u;            // -FIX(2.562915447)
+  z3 = 0u - z3 * 16069u;            // -FIX(1.961570560)
+  z4 = 0u - z4 * 3196u;             // -FIX(0.390180644)
+  z3 += z5;
+  z4 += z5;
+  tmp0 += z1 + z3;
+  tmp1 += z2 + z4;
+  tmp2 += z2 + z3;
+  tmp3 += z1 + z4;
+  const U rnd = (U)1 << (SHIFT - 1);
+  v[0] = (int32_t)(tmp10 + tmp3 + rnd) >> SHIFT;
+  v[7] = (int32_t)(tmp10 - tmp3 + rnd) >> SHIFT;
+  v[1] = (int32_t)(tmp11 + tmp2 + rnd) >> SHIFT;
+  v[6] = (int32_t)(tmp11 - tmp2 + rnd) >> SHIFT;
+  v[2] = (int32_t)(tmp12 + tmp1 + rnd) >> SHIFT;
+  v[5] = (int32_t)(tmp12 - tmp1 + rnd) >> SHIFT;
+  v[3] = (int32_t)(tmp13 + tmp0 + rnd) >> SHIFT;
+  v[4] = (int32_t)(tmp13 - tmp0 + rnd) >> SHIFT;
+}
+
+// level shift and clamp of a row-pass result
+AT_MJPG_HD uint32_t mjpg_pixel(int32_t v) {
+  v += 128;
+  return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// What the marker parser found.
+struct MjpgInfo {
+  int width, height;
+  int ncomp;          // 1 or 3
+  int hs, vs;         // luma sampling factors (1x1, 2x1, 2x2)
+  int restart;        // restart interval in MCUs (0: none)
+  int default_dht;    // a Huffman table slot was filled from the built-in Annex K tables
+};
+
+// Entropy decoder with its scratch memory (token and offset lists of one frame):
+// one per decoding thread, reused from frame to frame, so nothing is allocated per
+// frame once it has seen the largest frame.
+class MjpgDecoder {
+ public:
+  // Parses and entropy-decodes one JPEG.  want_w / want_h > 0: the picture must
+  // have exactly that size (kMjpgInvalid otherwise).  On success the luma tokens
+  // are held in this object until the next call; info() describes the stream.
+  int decode(const uint8_t* jpg, size_t len, int want_w, int want_h);
+  const MjpgInfo& info() const { return info_; }
+  uint32_t nblocks() const { return (uint32_t)(bw_ * bh_); }
+  // bytes pack() writes (header + payload in the smaller encoding)
+  size_t packed_bytes() const;
+  bool dense() const;
+  // Writes the coefficient stream of the decoded frame to dst (cap bytes, at least
+  // packed_bytes(); kMjpgHdrBytes + 128 * nblocks() always suffices).
+  int pack(uint8_t* dst, size_t cap) const;
+  // Full host decode: the luma plane (width x height) through the same integer IDCT.
+  int to_gray(uint8_t* gray, size_t cap) const;
+
+ private:
+  MjpgInfo info_{};
+  int bw_ = 0, bh_ = 0;              // visible block grid (ceil(width / 8), ceil(height / 8))
+  int gw_ = 0, gh_ = 0;              // decoded (MCU padded) luma block grid
+  uint16_t q_[64] = {0};             // luma quantisation table, natural order
+  std::vector<uint32_t> tok_;        // tokens in decode order
+  std::vector<uint32_t> start_;      // first token of each decoded block (decode order), + end
+  uint32_t kept_tokens_ = 0;         // tokens of the visible blocks
+  uint32_t decode_index(int bx, int by) const;
+};
+
+}  // namespace at
+
+// Host-only full decode to a luma plane (C ABI, exported from the library; the CPU
+// reference of the tests).  Returns 0 or a negative AT_E* code; *w / *h receive the
+// picture size as soon as the frame header has been parsed.
+extern "C" int at_mjpg_decode_gray_host(const uint8_t* jpg, size_t len, uint8_t* gray, size_t cap, int* w, int* h);
+// which encoding a frame of this stream takes on the link to a want_w x want_h detector
+// (0 x 0: any size): 0 sparse, 1 dense, < 0 the error at_enqueue_mjpg would give
+extern "C" int at_mjpg_stream_mode_host(const uint8_t* jpg, size_t len, int want_w, int want_h,
+                                        size_t* stream_bytes);
+
+#endif  // AT_MJPG_H_

@@ -23,7 +23,7 @@ AT_FMT_YUYV, AT_FMT_BGR8, AT_FMT_GRAY8 = 0, 1, 2
 (AT_STAGE_GRAY, AT_STAGE_DECIMATED, AT_STAGE_THRESHOLD, AT_STAGE_LABELS, AT_STAGE_SIZES,
  AT_STAGE_NUM_POINTS, AT_STAGE_NUM_PAIRS, AT_STAGE_QUADS, AT_STAGE_POINTS, AT_STAGE_BLOB_POINTS,
  AT_STAGE_NUM_PAIR_ENTRIES, AT_STAGE_PROBE) = range(12)
-AT_E_CAPACITY = -3
+AT_E_INVALID, AT_E_CAPACITY, AT_E_UNSUPPORTED = -1, -3, -6
 
 # Symbols declared in include/at_api.h (checked by tests/test_abi.py).
 EXPORTS = [
@@ -35,6 +35,8 @@ EXPORTS = [
     "at_gp_enable", "at_gp_tensor", "at_gp_copy", "at_gp_preprocess_device", "at_set_debug_taps",
     "at_draw_outlines_device", "at_detections", "at_max_detections", "at_annotate_staged", "at_enqueue_host",
     "at_kernel_span", "at_host_alloc", "at_host_free",
+    "at_enqueue_mjpg", "at_detect_mjpg", "at_detect_mjpg_batch", "at_mjpg_set_threads", "at_mjpg_stats",
+    "at_mjpg_decode_gray_host", "at_mjpg_stream_mode_host",
 ]
 
 TAG_SIZE = 0.1651  # metres, apriltags_cuda_detector.hpp:39
@@ -196,8 +198,59 @@ def load_library(path: str = LIB_PATH):
     if hasattr(L, "at_detections"):  # (A/B builds of older sources lack them)
         L.at_detections.argtypes = [C.c_void_p, C.c_int, C.POINTER(AtDetection), C.c_int]
         L.at_annotate_staged.argtypes = [C.c_void_p, C.c_int, C.POINTER(AtDetection), C.c_int, C.c_void_p]
+    if hasattr(L, "at_enqueue_mjpg"):  # (A/B builds of older sources lack the MJPG path)
+        L.at_enqueue_mjpg.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int,
+                                      C.POINTER(C.c_int)]
+        L.at_detect_mjpg.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(AtDetection), C.c_int,
+                                     C.POINTER(C.c_int)]
+        L.at_detect_mjpg_batch.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int,
+                                           C.POINTER(AtDetection), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.at_mjpg_set_threads.argtypes = [C.c_void_p, C.c_int]
+        L.at_mjpg_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.at_mjpg_decode_gray_host.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int)]
+        L.at_mjpg_stream_mode_host.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
     _LIB = L
     return L
+
+
+class MjpgError(RuntimeError):
+    """An MJPG frame the library refused: `code` is AT_E_UNSUPPORTED or AT_E_INVALID,
+    `frame` its index in the batch (None for the host-only calls)."""
+
+    def __init__(self, what, code, frame=None):
+        where = "" if frame is None else " (frame %d)" % frame
+        super().__init__("%s failed%s: %s (%d)" % (what, where, load_library().at_strerror(code).decode(), code))
+        self.code, self.frame = code, frame
+
+
+def mjpg_decode_gray(jpg: bytes):
+    """at_mjpg_decode_gray_host: the luma plane (H, W) uint8 of one baseline JPEG,
+    decoded on the host with the integer IDCT k_mjpg_idct runs (no device needed)."""
+    L = load_library()
+    jpg = bytes(jpg)
+    w, h = C.c_int(), C.c_int()
+    rc = L.at_mjpg_decode_gray_host(jpg, len(jpg), None, 0, C.byref(w), C.byref(h))
+    if rc < 0:
+        raise MjpgError("at_mjpg_decode_gray_host", rc)
+    out = np.empty((h.value, w.value), np.uint8)
+    rc = L.at_mjpg_decode_gray_host(jpg, len(jpg), out.ctypes.data, out.size, C.byref(w), C.byref(h))
+    if rc < 0:
+        raise MjpgError("at_mjpg_decode_gray_host", rc)
+    return out
+
+
+def mjpg_stream_mode(jpg: bytes, width: int = 0, height: int = 0):
+    """at_mjpg_stream_mode_host: ("sparse" | "dense", bytes on the link) of one frame on
+    its way to a width x height detector (0, 0: any size); raises MjpgError with the
+    code at_enqueue_mjpg would return for it."""
+    L = load_library()
+    jpg = bytes(jpg)
+    n = C.c_size_t()
+    rc = L.at_mjpg_stream_mode_host(jpg, len(jpg), int(width), int(height), C.byref(n))
+    if rc < 0:
+        raise MjpgError("at_mjpg_stream_mode_host", rc)
+    return ("dense" if rc else "sparse"), n.value
 
 
 def game_piece_preprocess_device(bgr_ptr: int, width: int, height: int, out_ptr: int, out_width: int = 640,
@@ -379,6 +432,53 @@ class GpuDetector:
         ptrs = (C.c_void_p * len(host_ptrs))(*host_ptrs)
         _check(load_library().at_enqueue_host(self._h, ptrs, len(host_ptrs), fmt), "at_enqueue_host")
         self._pending = len(host_ptrs)
+
+    # ---- MJPG camera frames (host entropy decode, k_mjpg_idct on the GPU) ------
+    def _mjpg_args(self, jpgs):
+        jpgs = [bytes(j) for j in jpgs]
+        ptrs = (C.c_char_p * len(jpgs))(*jpgs)
+        lens = (C.c_size_t * len(jpgs))(*[len(j) for j in jpgs])
+        return jpgs, ptrs, lens
+
+    def enqueue_mjpg(self, jpgs):
+        """at_enqueue_mjpg: a batch of JPEG frames (bytes); collect() later.  A frame the
+        library refuses raises MjpgError (its index and code) and enqueues nothing."""
+        _keep, ptrs, lens = self._mjpg_args(jpgs)
+        bad = C.c_int(-1)
+        rc = load_library().at_enqueue_mjpg(self._h, ptrs, lens, len(jpgs), C.byref(bad))
+        if rc in (AT_E_UNSUPPORTED, AT_E_INVALID):
+            raise MjpgError("at_enqueue_mjpg", rc, bad.value if bad.value >= 0 else None)
+        _check(rc, "at_enqueue_mjpg")
+        self._pending = len(jpgs)
+
+    def detect_mjpg_batch(self, jpgs):
+        """at_detect_mjpg_batch: JPEG frames in, detections per frame out (synchronous)."""
+        _keep, ptrs, lens = self._mjpg_args(jpgs)
+        bad = C.c_int(-1)
+        rc = load_library().at_detect_mjpg_batch(self._h, ptrs, lens, len(jpgs), self._out, self._cap, self._n,
+                                                 C.byref(bad))
+        self._last_status = rc
+        if rc in (AT_E_UNSUPPORTED, AT_E_INVALID):
+            raise MjpgError("at_detect_mjpg_batch", rc, bad.value if bad.value >= 0 else None)
+        if rc < 0 and rc != AT_E_CAPACITY:
+            _check(rc, "at_detect_mjpg_batch")
+        return self._unpack(len(jpgs))
+
+    def detect_mjpg(self, jpg: bytes):
+        """at_detect_mjpg: one JPEG frame, synchronous."""
+        return self.detect_mjpg_batch([jpg])[0]
+
+    def set_mjpg_threads(self, n: int):
+        """Host threads decoding the frames of one MJPG batch (1..16, default 1)."""
+        _check(load_library().at_mjpg_set_threads(self._h, int(n)), "at_mjpg_set_threads")
+
+    MJPG_STATS = ("compressed_bytes", "device_bytes", "dense_frames", "host_decode_us", "idct_kernel_ns")
+
+    def mjpg_stats(self):
+        """at_mjpg_stats of the last MJPG batch."""
+        buf = (C.c_uint64 * len(self.MJPG_STATS))()
+        n = _check(load_library().at_mjpg_stats(self._h, buf, len(buf)), "at_mjpg_stats")
+        return dict(zip(self.MJPG_STATS, [int(x) for x in buf[:n]]))
 
     def wait_stream(self, stream_handle: int):
         """at_stream_wait: the next enqueued batch waits (on the GPU) for the work queued

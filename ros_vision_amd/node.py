@@ -30,7 +30,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .detector import (AT_FMT_BGR8, AT_FMT_YUYV, TAG_SIZE, CameraMatrix, DistCoeffs, GpuDetector,
+from .detector import (AT_FMT_BGR8, AT_FMT_GRAY8, AT_FMT_YUYV, TAG_SIZE, CameraMatrix, DistCoeffs, GpuDetector,
                        tag_detections)
 
 PARAMETER_DEFAULTS = {
@@ -161,13 +161,19 @@ class ApriltagsDetectorNode:
             fn(payload)
 
     def image_callback(self, image, stamp_s, encoding="bgr8", receive_time_s=None):
-        """One frame: `image` is bgr8 [H, W, 3] (what cv_bridge hands the reference) or
-        yuyv [H, 2W]."""
+        """One frame: `image` is bgr8 [H, W, 3] (what cv_bridge hands the reference),
+        yuyv [H, 2W], mono8 [H, W], or -- encoding "jpeg" -- the bytes of one MJPG camera
+        frame (a sensor_msgs/CompressedImage's data): its luma is decoded on the way to
+        the GPU, poses and tables come out as for the other encodings, and no annotated
+        image is published (there is no colour image to draw on)."""
         start = time.perf_counter()
         latency_s = (receive_time_s if receive_time_s is not None else time.time()) - stamp_s
-        fmt = AT_FMT_BGR8 if encoding == "bgr8" else AT_FMT_YUYV
         det0 = time.perf_counter()
-        dets = self.detector.detect(np.ascontiguousarray(image), fmt)
+        if encoding == "jpeg":
+            dets = self.detector.detect_mjpg(bytes(image))
+        else:
+            fmt = {"bgr8": AT_FMT_BGR8, "mono8": AT_FMT_GRAY8}.get(encoding, AT_FMT_YUYV)
+            dets = self.detector.detect(np.ascontiguousarray(image), fmt)
         det1 = time.perf_counter()
         poses = self.detector.poses()
         res = FrameResult()
