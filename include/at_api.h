@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define AT_ABI_VERSION 6
+#define AT_ABI_VERSION 7
 
 enum {
   AT_OK = 0,
@@ -135,7 +135,8 @@ int at_enqueue_host(at_detector *d, const uint8_t *const *frames, int nframes, a
  * detector's.  Otherwise it continues like at_enqueue_host with GRAY8 frames;
  * at_collect, at_poses, at_detections, at_frame_status and at_debug_copy follow as
  * usual (AT_STAGE_GRAY with the taps on is the decoded plane).  at_annotate_staged
- * after an MJPG batch is AT_E_INVALID: there is no chroma on the device.
+ * after an MJPG batch is AT_E_INVALID unless colour was on (at_mjpg_set_color): there
+ * is no chroma on the device then.
  * The host decode waits for nothing, so called while the batch before is still running
  * it overlaps that batch (two staging sets); like every enqueue it then waits for a
  * batch not yet collected before it reuses the result buffers.
@@ -152,13 +153,35 @@ int at_mjpg_set_threads(at_detector *d, int n);
  * is on and known once the batch is collected, 0 otherwise).
  * Returns the number of entries written. */
 int at_mjpg_stats(at_detector *d, uint64_t *out, int cap);
+/* Colour (off by default; takes effect from the next at_enqueue_mjpg): the host keeps the
+ * Cb and Cr coefficients too and sends them behind the luma ones (each component with
+ * its own quantisation table), the GPU runs the same IDCT on the two chroma planes,
+ * upsamples them (libjpeg's "fancy" triangle filter for 4:2:2 and 4:2:0) and converts
+ * to BGR8.  The image equals libjpeg-turbo's default decode bit for bit (a
+ * single-component frame gives B = G = R = Y).  The detection reads the same luma plane
+ * as with colour off.  After a batch enqueued with colour on:
+ *   at_mjpg_bgr gives frame `frame`'s BGR8 image (width x height x 3, row-major) in device
+ *   memory, valid until the next batch (the no-copy hand-off, like at_gp_tensor);
+ *   at_mjpg_copy_bgr copies it to the host (cap >= width * height * 3);
+ *   at_annotate_staged draws on that image and copies it out (it is consumed);
+ *   with at_gp_enable, at_gp_tensor / at_gp_copy serve the batch's game-piece tensors,
+ *   computed from those images.
+ * Both return AT_E_INVALID unless the last batch was such a batch (whatever the setting
+ * is now) and `frame` is one of its frames.  at_mjpg_stats [5]: the time of the two
+ * colour kernels (chroma IDCT, upsampling + conversion) in nanoseconds, measured like [4]. */
+int at_mjpg_set_color(at_detector *d, int enable);
+int at_mjpg_bgr(at_detector *d, int frame, const uint8_t **dev_ptr);
+int at_mjpg_copy_bgr(at_detector *d, int frame, uint8_t *dst, size_t cap);
 /* Host only, no device needed: the full luma decode of one such JPEG (any size up to
  * 2^26 pixels) with the same integer IDCT the kernel runs -- the CPU reference of the
  * MJPG path.  *w / *h (may be NULL) receive the picture size; gray == NULL parses the
  * frame header only.  at_mjpg_stream_mode_host tells how the frame would travel to a
  * want_w x want_h detector (0, 0: any size): 0 sparse, 1 dense, < 0 the error
- * at_enqueue_mjpg would return; *stream_bytes (may be NULL) its size on the link. */
+ * at_enqueue_mjpg would return; *stream_bytes (may be NULL) its size on the link (with
+ * colour off).  at_mjpg_decode_bgr_host is the full colour decode to BGR8 (cap >= 3 * w * h)
+ * through the arithmetic the colour kernels share -- their CPU reference. */
 int at_mjpg_decode_gray_host(const uint8_t *jpg, size_t len, uint8_t *gray, size_t cap, int *w, int *h);
+int at_mjpg_decode_bgr_host(const uint8_t *jpg, size_t len, uint8_t *bgr, size_t cap, int *w, int *h);
 int at_mjpg_stream_mode_host(const uint8_t *jpg, size_t len, int want_w, int want_h, size_t *stream_bytes);
 
 /* Stream ordering without a host wait: the detector's next enqueued batch starts
@@ -290,7 +313,7 @@ int at_tag_detections(const at_pose *poses, int n, const double *extr_R, const d
  * later batch of AT_FMT_BGR8 frames); at_gp_tensor gives frame `frame`'s tensor of
  * the last batch in device memory (channels x out_height x out_width floats, valid
  * until the next batch); at_gp_copy copies it to the host.  AT_E_INVALID when the
- * last batch was not BGR8.  at_gp_preprocess_device runs it standalone on one
+ * last batch was neither BGR8 nor a colour-on MJPG batch.  at_gp_preprocess_device runs it standalone on one
  * device-resident BGR8 image on `stream` (a hipStream_t, NULL = default stream). */
 int at_gp_enable(at_detector *d, int out_width, int out_height, int channels);
 int at_gp_tensor(at_detector *d, int frame, const float **dev_ptr);
@@ -313,7 +336,8 @@ int at_draw_outlines_device(at_detector *d, const at_detection *dets, int n, uin
  * redraw: draws those outlines onto frame `frame` of the last batch where
  * at_detect / at_detect_batch staged it in HBM, and copies the annotated image
  * (width x height x 3) to `bgr_out` in host memory.  AT_E_INVALID unless the last
- * batch was host BGR8 frames.  The staged copy is consumed (overwritten). */
+ * batch was host BGR8 frames or a colour-on MJPG batch (then the decoded image is what
+ * is drawn on).  The staged copy is consumed (overwritten). */
 int at_annotate_staged(at_detector *d, int frame, const at_detection *dets, int n, uint8_t *bgr_out);
 
 /* Page-locked host memory (hipHostMalloc) for buffers the detector copies into on

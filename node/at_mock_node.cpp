@@ -7,11 +7,13 @@
 // ApriltagsDetector::imageCallback hands its cv_bridge image to the detector
 // (apriltags_cuda_detector.cu:382-557).  Publishers print one JSON line per
 // frame; --proto-out / --image-out write the ApriltagListProto bytes and the
-// outlined bgr8 image of the last frame.
+// outlined bgr8 image of the last frame (bgr8 input, or MJPG with --mjpg-color: the
+// frame's colour is then decoded on the GPU too).
 //
 // usage: at_mock_node --camera-serial S --format bgr8|yuyv|gray|mjpg --frames F [--count N]
 //        [--vision-config-dir D] [--pin-to-core C --priority P]
 //        [--measurement-csv PATH] [--proto-out P] [--image-out I] [--device K] [--time N]
+//        [--mjpg-color]
 //   As the reference node (apriltags_cuda_detector.cu:137-193): the frame size, the
 //   intrinsics and the extrinsics come from the camera serial's records in the
 //   vision_config_data share directory, found through $AMENT_PREFIX_PATH
@@ -82,8 +84,16 @@ std::vector<Span> split_mjpg(const std::vector<uint8_t>& d) {
 int main(int argc, char** argv) {
   int W = 0, H = 0, count = -1, device = 0, pin = -1, priority = 80, time_n = 0;
   std::string fmt_s = "yuyv", frames_path, calib_dir, serial = "N/A", sys_cfg, csv, proto_out, image_out, share_dir;
-  for (int i = 1; i + 1 < argc; i += 2) {
-    const std::string k = argv[i], v = argv[i + 1];
+  bool mjpg_color = false;
+  for (int i = 1; i < argc; i += 2) {
+    const std::string k = argv[i];
+    if (k == "--mjpg-color") {  // (the one option without a value)
+      mjpg_color = true;
+      i -= 1;
+      continue;
+    }
+    if (i + 1 >= argc) break;
+    const std::string v = argv[i + 1];
     if (k == "--width") W = std::atoi(v.c_str());
     else if (k == "--height") H = std::atoi(v.c_str());
     else if (k == "--format") fmt_s = v;
@@ -166,11 +176,12 @@ int main(int argc, char** argv) {
     core.publish_robot = on_robot;
     core.publish_camera = on_camera;
     core.ctx = &sink;
+    if (mjpg && mjpg_color) core.set_mjpg_color(true);
     at_node::FrameOutputs out;
     at_node::ImageBuffer image;
     auto run = [&](int f, double stamp) {
       const uint8_t* p = all.data() + spans[(size_t)f].off;
-      if (mjpg) return core.process_compressed(p, spans[(size_t)f].len, stamp, stamp, &out);
+      if (mjpg) return core.process_compressed(p, spans[(size_t)f].len, stamp, stamp, &out, &image);
       return core.process(p, fmt, stamp, stamp, &out, fmt == AT_FMT_BGR8 ? &image : nullptr);
     };
     if (time_n > 0) {  // the node's per-frame path, timed

@@ -497,8 +497,14 @@ int DetectorCore::process(const uint8_t* frame, at_pixfmt fmt, double stamp_s, d
 }
 
 int DetectorCore::process_compressed(const uint8_t* data, size_t len, double stamp_s, double receive_s,
-                                     FrameOutputs* out) {
-  return run(data, len, -1, stamp_s, receive_s, out, nullptr);
+                                     FrameOutputs* out, ImageBuffer* annotate) {
+  return run(data, len, -1, stamp_s, receive_s, out, mjpg_color_ ? annotate : nullptr);
+}
+
+void DetectorCore::set_mjpg_color(bool on) {
+  const int rc = at_mjpg_set_color(det_, on ? 1 : 0);
+  if (rc != AT_OK) throw std::runtime_error(std::string("at_mjpg_set_color: ") + at_strerror(rc));
+  mjpg_color_ = on;
 }
 
 // fmt < 0: `frame` is one MJPG frame of `len` bytes (at_detect_mjpg); the tail is the same
@@ -531,9 +537,10 @@ int DetectorCore::run(const uint8_t* frame, size_t len, int fmt, double stamp_s,
     out->robot.push_back({d.id, d.robot[0], d.robot[1], d.robot[2]});
   }
   out->proto = encode_apriltag_list(out->tags.data(), (int)out->tags.size(), stamp_s);
-  if (annotate && fmt == AT_FMT_BGR8) {
+  if (annotate && (fmt == AT_FMT_BGR8 || fmt < 0)) {
     // draw_detection_outlines (:411) on the GPU, on the copy of the frame at_detect
-    // staged in HBM: no host copy of the frame, no host drawing
+    // staged in HBM: no host copy of the frame, no host drawing (an MJPG frame with
+    // colour on: on the image decoded there)
     annotate->resize((size_t)width_ * height_ * 3);
     const int arc = at_annotate_staged(det_, 0, out->detections.data(), n, annotate->data());
     if (arc != AT_OK) return arc;

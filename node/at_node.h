@@ -231,10 +231,15 @@ class DetectorCore {
   int process(const uint8_t* frame, at_pixfmt fmt, double stamp_s, double receive_s, FrameOutputs* out,
               ImageBuffer* annotate = nullptr);
   // One MJPG camera frame (a sensor_msgs/CompressedImage's data: one baseline JPEG of
-  // the detector's size): at_detect_mjpg, then the same tail.  No annotated image:
-  // only luma reaches the GPU.  AT_E_UNSUPPORTED / AT_E_INVALID for a stream the
-  // library refuses (nothing is published then).
-  int process_compressed(const uint8_t* data, size_t len, double stamp_s, double receive_s, FrameOutputs* out);
+  // the detector's size): at_detect_mjpg, then the same tail.  AT_E_UNSUPPORTED /
+  // AT_E_INVALID for a stream the library refuses (nothing is published then).
+  // By default only luma reaches the GPU and there is no annotated image.  After
+  // set_mjpg_color(true) the frame's colour is decoded on the GPU too (at_mjpg_set_color)
+  // and `annotate` (may be null) receives the outlined image as process() gives it for
+  // bgr8, drawn on the decoded image in HBM; it goes to the publisher queue likewise.
+  int process_compressed(const uint8_t* data, size_t len, double stamp_s, double receive_s, FrameOutputs* out,
+                         ImageBuffer* annotate = nullptr);
+  void set_mjpg_color(bool on);
 
   const Params& params() const { return params_; }
   int width() const { return width_; }
@@ -261,6 +266,7 @@ class DetectorCore {
           ImageBuffer* annotate);
   int width_, height_;
   Params params_;
+  bool mjpg_color_ = false;
   struct StampedImage {
     std::vector<uint8_t> bgr;
     double stamp_s = 0;

@@ -31,6 +31,9 @@ hipError_t launch_gp_preprocess(const uint8_t* src, int w, int h, float* out, in
 hipError_t launch_draw(const DrawPrim* prims, int n, uint32_t* last, uint8_t* bgr, int W, int H, hipStream_t st);
 hipError_t launch_mjpg_idct(const uint8_t* coef, size_t slot, uint8_t* out, size_t out_stride, int W, int H,
                             int nframes, hipStream_t st);
+hipError_t launch_mjpg_color(const uint8_t* coef, size_t slot, const uint8_t* gray, uint8_t* planes,
+                             size_t plane_stride, uint8_t* bgr, size_t img_stride, int W, int H, int nframes,
+                             hipStream_t st);
 hipError_t prepare_kernels(const Geom& g);
 hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, int B, int fmt, int nblobwg,
                            hipStream_t st, hipEvent_t* ev, hipStream_t st2, hipEvent_t fork, hipEvent_t join,
@@ -163,7 +166,8 @@ struct at_detector {
   int last_gray;            // the last batch wrote the gray plane (AT_STAGE_GRAY)
   int last_sizes;           // ... and the size plane (AT_STAGE_SIZES)
   int last_staged;          // the last batch's frames were host frames staged in d_in (at_detect*)
-  int last_gp;              // the last batch ran the game-piece preprocessing (k_gp_pre)
+  int last_gp;              // the last batch produced the game-piece tensors (k_gp_pre; a colour MJPG batch: k_gp_pre_one)
+  int last_mj_color;        // the last batch was an MJPG batch enqueued with colour on (d_mj_bgr holds its images)
   int pending;
   hipEvent_t ev_done;
   hipEvent_t ev_ext;                      // at_stream_wait: recorded on the producer's stream
@@ -199,9 +203,18 @@ struct at_detector {
   std::vector<int> mj_rc;
   std::vector<size_t> mj_bytes;   // per frame: bytes of its coefficient stream
   std::vector<uint8_t> mj_dense;  // ... and whether it took the dense encoding
-  uint64_t mj_stats[5];     // last MJPG batch: compressed bytes, bytes sent, dense frames, decode us, kernel ns
-  hipEvent_t ev_mj[2];      // around k_mjpg_idct while stage profiling is on (created on first use)
-  int mj_timed;             // the pending batch recorded them
+  uint64_t mj_stats[6];     // last MJPG batch: compressed bytes, bytes sent, dense frames, decode us, kernel ns,
+                            // colour kernels ns
+  hipEvent_t ev_mj[3];      // around k_mjpg_idct, and after the colour kernels, while stage profiling is on
+                            // (created on first use)
+  int mj_timed;             // the pending batch recorded them (2: the colour one too)
+  // colour (at_mjpg_set_color), allocated on the first colour-on MJPG call, when the slots above
+  // grow to hold the chroma sub-streams: two chroma planes per frame and the BGR8 images
+  int mj_color;             // the setting; takes effect at the next at_enqueue_mjpg
+  int mj_color_bufs;        // the buffers are the colour-sized ones
+  uint8_t* d_mj_planes;     // [B][2][mj_plane]
+  size_t mj_plane;
+  uint8_t* d_mj_bgr;        // [B][in_stride]
 };
 
 // Experiment and diagnostic knobs (stage cut-offs, grid / tile overrides, phase
@@ -756,6 +769,7 @@ static int enqueue(at_detector* d, int nframes, int fmt) {
   d->last_gray = fmt == AT_FMT_BGR8 || d->prm.taps;  // (YUYV / GRAY8: k_decode samples the frame)
   d->last_sizes = d->g.ctw == 32 || d->prm.taps;     // (throughput mode: the size plane for the taps only)
   d->last_gp = d->prm.gp_c && fmt == AT_FMT_BGR8;
+  d->last_mj_color = 0;  // (at_enqueue_mjpg sets it after a colour-on batch)
   d->pending = 1;
   return AT_OK;
 }
@@ -783,6 +797,10 @@ static int collect(at_detector* d, at_detection* out, int cap_per_frame, int* n_
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, d->ev_mj[0], d->ev_mj[1]));
     d->mj_stats[4] = (uint64_t)((double)ms * 1e6);
+    if (d->mj_timed == 2) {
+      HIPCHK(hipEventElapsedTime(&ms, d->ev_mj[1], d->ev_mj[2]));
+      d->mj_stats[5] = (uint64_t)((double)ms * 1e6);
+    }
     d->mj_timed = 0;
   }
   if (d->kt.stage >= 0) {
@@ -896,21 +914,51 @@ int at_detect(at_detector* d, const uint8_t* frame, at_pixfmt fmt, at_detection*
 // frame leaves the detector as it was.  Then the coefficient streams go to the device,
 // k_mjpg_idct writes the GRAY8 planes into the frames' staging slots, and the batch
 // continues as host-fed GRAY8 frames (the captured launch sequence is the GRAY8 one).
-static int mjpg_prepare(at_detector* d) {
-  if (d->d_mj) return AT_OK;
+// With colour on (at_mjpg_set_color) the chroma coefficients travel behind the luma ones
+// and two more launches in front of the graph leave each frame's BGR8 image in d_mj_bgr.
+//
+// The buffers, allocated on first use.  color: the slots also hold the chroma sub-streams (worst case 4:4:4, all three planes
+// dense), and the chroma planes and BGR8 images exist.  Luma-only buffers from earlier
+// colour-off batches are replaced (after a pending batch, whose copies read them).
+static int mjpg_prepare(at_detector* d, bool color) {
+  if (d->d_mj && (!color || d->mj_color_bufs)) return AT_OK;
   const size_t nb = (size_t)(d->g.W / 8) * (d->g.H / 8);
-  const size_t slot = ((size_t)kMjpgHdrBytes + 128 * nb + 255) & ~(size_t)255;
+  const size_t slot = ((color ? at::MjpgDecoder::slot_bytes(d->g.W, d->g.H, true) : (size_t)kMjpgHdrBytes + 128 * nb) +
+                       255) & ~(size_t)255;
   const size_t total = slot * (size_t)d->B;
+  const size_t plane = ((size_t)d->g.W * d->g.H + 255) & ~(size_t)255;
   uint8_t* h[2] = {nullptr, nullptr};
-  void* dev = nullptr;
+  void *dev = nullptr, *planes = nullptr, *bgr = nullptr;
+  if (d->d_mj && d->pending) HIPCHK(hipEventSynchronize(d->ev_done));
   if (hipHostMalloc((void**)&h[0], total, hipHostMallocDefault) != hipSuccess ||
       hipHostMalloc((void**)&h[1], total, hipHostMallocDefault) != hipSuccess ||
-      hipMalloc(&dev, total) != hipSuccess) {
+      hipMalloc(&dev, total) != hipSuccess ||
+      (color && (hipMalloc(&planes, 2 * plane * (size_t)d->B) != hipSuccess ||
+                 hipMalloc(&bgr, d->in_stride * (size_t)d->B) != hipSuccess))) {
     if (h[0]) (void)hipHostFree(h[0]);
     if (h[1]) (void)hipHostFree(h[1]);
+    if (dev) (void)hipFree(dev);
+    if (planes) (void)hipFree(planes);
     return AT_E_NOMEM;
   }
+  if (d->d_mj) {  // the luma-only set
+    for (auto& a : d->allocs)
+      if (a == d->d_mj) a = nullptr;
+    (void)hipFree(d->d_mj);
+    for (uint8_t*& p : d->mj_host) {
+      (void)hipHostFree(p);
+      p = nullptr;
+    }
+  }
   d->allocs.push_back(dev);
+  if (color) {
+    d->allocs.push_back(planes);
+    d->allocs.push_back(bgr);
+    d->d_mj_planes = (uint8_t*)planes;
+    d->d_mj_bgr = (uint8_t*)bgr;
+    d->mj_plane = plane;
+    d->mj_color_bufs = 1;
+  }
   d->d_mj = (uint8_t*)dev;
   d->mj_host[0] = h[0];
   d->mj_host[1] = h[1];
@@ -929,9 +977,15 @@ int at_mjpg_set_threads(at_detector* d, int n) {
   return AT_OK;
 }
 
+int at_mjpg_set_color(at_detector* d, int enable) {
+  if (!d) return AT_E_INVALID;
+  d->mj_color = enable ? 1 : 0;
+  return AT_OK;
+}
+
 int at_mjpg_stats(at_detector* d, uint64_t* out, int cap) {
   if (!d || !out || cap < 1) return AT_E_INVALID;
-  const int n = std::min(cap, 5);
+  const int n = std::min(cap, 6);
   for (int i = 0; i < n; i++) out[i] = d->mj_stats[i];
   return n;
 }
@@ -945,7 +999,8 @@ int at_enqueue_mjpg(at_detector* d, const uint8_t* const* jpgs, const size_t* le
       return AT_E_INVALID;
     }
   HIPCHK(hipSetDevice(d->device));
-  const int prc = mjpg_prepare(d);
+  const bool color = d->mj_color != 0;
+  const int prc = mjpg_prepare(d, color);
   if (prc != AT_OK) return prc;
   const int set = d->mj_cur ^ 1;
   uint8_t* stage = d->mj_host[set];
@@ -954,7 +1009,7 @@ int at_enqueue_mjpg(at_detector* d, const uint8_t* const* jpgs, const size_t* le
   auto work = [&](int t) {
     at::MjpgDecoder& dec = d->mj_dec[(size_t)t];
     for (int f = t; f < nframes; f += nthr) {
-      int rc = dec.decode(jpgs[f], lens[f], d->g.W, d->g.H);
+      int rc = dec.decode(jpgs[f], lens[f], d->g.W, d->g.H, color);
       if (rc == AT_OK) {
         d->mj_bytes[(size_t)f] = dec.packed_bytes();
         rc = dec.pack(stage + (size_t)f * d->mj_slot, d->mj_slot);
@@ -978,7 +1033,7 @@ int at_enqueue_mjpg(at_detector* d, const uint8_t* const* jpgs, const size_t* le
       return d->mj_rc[(size_t)f];  // nothing enqueued, the staging set in use untouched
     }
   if (d->pending) HIPCHK(hipEventSynchronize(d->ev_done));  // the frame table and result buffers are reused
-  uint64_t st[5] = {0, 0, 0, (uint64_t)(t1 - t0), 0};
+  uint64_t st[6] = {0, 0, 0, (uint64_t)(t1 - t0), 0, 0};
   for (int f = 0; f < nframes; f++) {
     const size_t nbytes = d->mj_bytes[(size_t)f];
     st[0] += lens[f];
@@ -997,11 +1052,44 @@ int at_enqueue_mjpg(at_detector* d, const uint8_t* const* jpgs, const size_t* le
   }
   HIPCHK(launch_mjpg_idct(d->d_mj, d->mj_slot, d->d_in, d->in_stride, d->g.W, d->g.H, nframes, d->st));
   if (timed) HIPCHK(hipEventRecord(d->ev_mj[1], d->st));
-  d->mj_timed = timed;
+  if (color) {
+    // the chroma planes and the BGR8 images, then the game-piece tensors from those
+    HIPCHK(launch_mjpg_color(d->d_mj, d->mj_slot, d->d_in, d->d_mj_planes, d->mj_plane, d->d_mj_bgr, d->in_stride,
+                             d->g.W, d->g.H, nframes, d->st));
+    if (timed) HIPCHK(hipEventRecord(d->ev_mj[2], d->st));
+    if (d->prm.gp_c)
+      for (int f = 0; f < nframes; f++)
+        HIPCHK(launch_gp_preprocess(d->d_mj_bgr + (size_t)f * d->in_stride, d->g.W, d->g.H,
+                                    d->d.gp_out + (size_t)f * d->prm.gp_c * d->prm.gp_w * d->prm.gp_h, d->prm.gp_w,
+                                    d->prm.gp_h, d->prm.gp_c, d->st));
+  }
+  d->mj_timed = timed ? (color ? 2 : 1) : 0;
   const int rc = enqueue(d, nframes, AT_FMT_GRAY8);
   if (rc) return rc;
   d->last_staged = 1;
+  d->last_mj_color = color;
+  d->last_gp = color && d->prm.gp_c;
   memcpy(d->mj_stats, st, sizeof(st));
+  return AT_OK;
+}
+
+int at_mjpg_bgr(at_detector* d, int frame, const uint8_t** dev_ptr) {
+  if (!d || !dev_ptr || !d->last_mj_color || frame < 0 || frame >= d->last_nframes) return AT_E_INVALID;
+  *dev_ptr = d->d_mj_bgr + (size_t)frame * d->in_stride;
+  return AT_OK;
+}
+
+int at_mjpg_copy_bgr(at_detector* d, int frame, uint8_t* dst, size_t cap) {
+  const uint8_t* src = nullptr;
+  const int rc = at_mjpg_bgr(d, frame, &src);
+  if (rc != AT_OK) return rc;
+  const size_t n = (size_t)d->g.W * d->g.H * 3;
+  if (!dst || cap < n) return AT_E_INVALID;
+  HIPCHK(hipSetDevice(d->device));
+  if (d->pending) HIPCHK(hipEventSynchronize(d->ev_done));
+  // on the detector's own stream (no null-stream copy), in order behind k_mjpg_bgr
+  HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, d->st));
+  HIPCHK(hipStreamSynchronize(d->st));
   return AT_OK;
 }
 
@@ -1258,10 +1346,12 @@ int at_draw_outlines_device(at_detector* d, const at_detection* dets, int n, uin
 
 int at_annotate_staged(at_detector* d, int frame, const at_detection* dets, int n, uint8_t* bgr_out) {
   if (!d || !bgr_out || n < 0 || (n > 0 && !dets)) return AT_E_INVALID;
-  if (!d->last_staged || d->last_fmt != AT_FMT_BGR8 || frame < 0 || frame >= d->last_nframes) return AT_E_INVALID;
+  if (!d->last_staged || (d->last_fmt != AT_FMT_BGR8 && !d->last_mj_color) || frame < 0 || frame >= d->last_nframes)
+    return AT_E_INVALID;
   HIPCHK(hipSetDevice(d->device));
   if (d->pending) HIPCHK(hipEventSynchronize(d->ev_done));
-  uint8_t* img = d->d_in + (size_t)frame * d->in_stride;
+  // a colour MJPG batch: the frame's decoded image (its d_in slot holds the gray plane)
+  uint8_t* img = (d->last_mj_color ? d->d_mj_bgr : d->d_in) + (size_t)frame * d->in_stride;
   const int rc = draw_outlines(d, dets, n, img);
   if (rc != AT_OK) return rc;
   // in stream order after the drawing, on the detector's stream (no null-stream copy);

@@ -5413,12 +5413,10 @@ hipError_t launch_draw(const DrawPrim* prims, int n, uint32_t* last, uint8_t* bg
 constexpr int kMjpgBlocksPerWg = 32, kMjpgLdsStride = 72;
 __constant__ uint8_t c_mjpg_zigzag[64] = AT_MJPG_ZIGZAG;
 
-__global__ __launch_bounds__(256) void k_mjpg_idct(const uint8_t* __restrict__ coef, size_t slot,
-                                                   uint8_t* __restrict__ out, size_t out_stride, int W, int bw,
-                                                   uint32_t nb) {
-  __shared__ __attribute__((aligned(16))) int32_t ws[kMjpgBlocksPerWg * kMjpgLdsStride];
-  const int f = blockIdx.y;
-  const uint8_t* fr = coef + (size_t)f * slot;
+// The workgroup's 32 blocks of one plane's stream `fr` (header + payload) into the
+// plane `out` (row stride W bytes, bw blocks per row, nb blocks in all).
+__device__ __forceinline__ void mjpg_idct_blocks(const uint8_t* __restrict__ fr, uint8_t* __restrict__ out, int W,
+                                                 int bw, uint32_t nb, int32_t* ws) {
   const uint16_t* q = reinterpret_cast<const uint16_t*>(fr);
   const uint32_t mode = *reinterpret_cast<const uint32_t*>(fr + kMjpgModeOff);
   const uint32_t ntok = *reinterpret_cast<const uint32_t*>(fr + kMjpgNtokOff);
@@ -5479,9 +5477,114 @@ __global__ __launch_bounds__(256) void k_mjpg_idct(const uint8_t* __restrict__ c
     px.y = mjpg_pixel(v[4]) | (mjpg_pixel(v[5]) << 8) | (mjpg_pixel(v[6]) << 16) | (mjpg_pixel(v[7]) << 24);
     if (blk < nb) {
       const uint32_t by = blk / (uint32_t)bw, bx = blk - by * (uint32_t)bw;
-      *reinterpret_cast<uint2*>(out + (size_t)f * out_stride + ((size_t)by * 8 + r) * W + (size_t)bx * 8) = px;
+      *reinterpret_cast<uint2*>(out + ((size_t)by * 8 + r) * W + (size_t)bx * 8) = px;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void k_mjpg_idct(const uint8_t* __restrict__ coef, size_t slot,
+                                                   uint8_t* __restrict__ out, size_t out_stride, int W, int bw,
+                                                   uint32_t nb) {
+  __shared__ __attribute__((aligned(16))) int32_t ws[kMjpgBlocksPerWg * kMjpgLdsStride];
+  const int f = blockIdx.y;
+  mjpg_idct_blocks(coef + (size_t)f * slot, out + (size_t)f * out_stride, W, bw, nb, ws);
+}
+
+// Colour on: the same over the Cb (blockIdx.z = 0) and Cr (1) sub-streams of every frame,
+// into the frame's two chroma planes of 8 * bw x 8 * bh bytes (the whole block grid: the
+// padding beyond the cw x ch real samples is written and never read).  The geometry is
+// the sub-stream header's, so one batch may mix samplings; the grid is sized for the
+// largest plane (max_nb blocks, 4:4:4) and the surplus workgroups exit, as do all of a
+// single-component frame (no sub-streams: offset 0).
+__global__ __launch_bounds__(256) void k_mjpg_idct_chroma(const uint8_t* __restrict__ coef, size_t slot,
+                                                          uint8_t* __restrict__ planes, size_t plane_stride,
+                                                          uint32_t max_nb) {
+  __shared__ __attribute__((aligned(16))) int32_t ws[kMjpgBlocksPerWg * kMjpgLdsStride];
+  const int f = blockIdx.y, c = blockIdx.z;
+  const uint8_t* fr = coef + (size_t)f * slot;
+  const uint32_t off = *reinterpret_cast<const uint32_t*>(fr + (c ? kMjpgCrOff : kMjpgCbOff));
+  if (!off || (size_t)off + kMjpgHdrBytes > slot) return;
+  const uint8_t* sub = fr + off;
+  // (the host wrote these; the clamps keep a wrong header inside the plane all the same)
+  uint32_t nb = min(*reinterpret_cast<const uint32_t*>(sub + kMjpgNblkOff), max_nb);
+  const uint32_t bw = max(1u, min(*reinterpret_cast<const uint32_t*>(sub + kMjpgBwOff), nb));
+  nb -= nb % bw;  // whole block rows
+  if (blockIdx.x * kMjpgBlocksPerWg >= nb) return;
+  mjpg_idct_blocks(sub, planes + ((size_t)f * 2 + c) * plane_stride, 8 * (int)bw, (int)bw, nb, ws);
+}
+
+// Colour on: BGR8 [H][W][3] of every frame from its luma plane (the GRAY8 slot
+// k_mjpg_idct wrote) and its two chroma planes: libjpeg's fancy upsampling per the
+// frame's sampling (mjpg_up_h2v1 / mjpg_up_h2v2; the neighbour beyond the first / last
+// real chroma sample or row is that sample or row itself, never the block padding) and
+// its fixed-point colour conversion (mjpg_bgr).  Integers only.
+//
+// One lane takes 4 consecutive pixels of one row (W % 8 == 0): the Y load is one dword,
+// consecutive lanes consecutive dwords; the 12 BGR bytes go out as one 3-dword store,
+// consecutive lanes 12 bytes apart, so a wave writes 768 contiguous bytes.  Chroma per
+// plane (and per row, two for 4:2:0): 4:4:4 one dword; subsampled the lane's two
+// samples as one 16-bit load and the two neighbours as byte loads (clamped columns).
+// Workgroup 64 x 4: a wave is 256 pixels of a row, the 4 waves 4 rows (the two rows of
+// a 4:2:0 pair share their chroma rows in L1/L2).
+__global__ __launch_bounds__(256) void k_mjpg_bgr(const uint8_t* __restrict__ coef, size_t slot,
+                                                  const uint8_t* __restrict__ gray, const uint8_t* __restrict__ planes,
+                                                  size_t plane_stride, uint8_t* __restrict__ bgr, size_t img_stride,
+                                                  int W, int H) {
+  const int f = blockIdx.z;
+  const int x0 = 4 * (int)(blockIdx.x * 64 + threadIdx.x), y = (int)(blockIdx.y * 4 + threadIdx.y);
+  if (x0 >= W || y >= H) return;
+  const uint32_t samp = *reinterpret_cast<const uint32_t*>(coef + (size_t)f * slot + kMjpgSampOff);
+  const int hs = (samp & 0xff) == 2 ? 2 : 1, vs = ((samp >> 8) & 0xff) == 2 ? 2 : 1, ncomp = (int)(samp >> 16);
+  const uint32_t yy = *reinterpret_cast<const uint32_t*>(gray + (size_t)f * img_stride + (size_t)y * W + x0);
+  int32_t cv[2][4];
+  if (ncomp != 3) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) cv[0][k] = cv[1][k] = 128;
+  } else {
+    const int cw = W / hs, ch = H / vs;            // real chroma samples (W, H are multiples of 8)
+    const int cstride = ((cw + 7) >> 3) << 3;      // the plane's row: whole blocks
+    const int j = y / vs;
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+      const uint8_t* a = planes + ((size_t)f * 2 + c) * plane_stride + (size_t)j * cstride;
+      if (hs == 1) {
+        const uint32_t v = *reinterpret_cast<const uint32_t*>(a + x0);
+#pragma unroll
+        for (int k = 0; k < 4; k++) cv[c][k] = (int32_t)((v >> (8 * k)) & 0xff);
+      } else {
+        const int i0 = x0 >> 1;
+        const int il = max(i0 - 1, 0), ir = min(i0 + 2, cw - 1);
+        const uint32_t m = *reinterpret_cast<const uint16_t*>(a + i0);
+        int32_t s[4] = {(int32_t)a[il], (int32_t)(m & 0xff), (int32_t)(m >> 8), (int32_t)a[ir]};
+        if (vs == 2) {
+          const int n = (y & 1) ? min(j + 1, ch - 1) : max(j - 1, 0);
+          const uint8_t* an = a + ((ptrdiff_t)n - j) * cstride;
+          const uint32_t mn = *reinterpret_cast<const uint16_t*>(an + i0);
+          const int32_t t[4] = {(int32_t)an[il], (int32_t)(mn & 0xff), (int32_t)(mn >> 8), (int32_t)an[ir]};
+#pragma unroll
+          for (int k = 0; k < 4; k++) s[k] = 3 * s[k] + t[k];
+          cv[c][0] = mjpg_up_h2v2(s[1], s[0], 0);
+          cv[c][1] = mjpg_up_h2v2(s[1], s[2], 1);
+          cv[c][2] = mjpg_up_h2v2(s[2], s[1], 0);
+          cv[c][3] = mjpg_up_h2v2(s[2], s[3], 1);
+        } else {
+          cv[c][0] = mjpg_up_h2v1(s[1], s[0], 0);
+          cv[c][1] = mjpg_up_h2v1(s[1], s[2], 1);
+          cv[c][2] = mjpg_up_h2v1(s[2], s[1], 0);
+          cv[c][3] = mjpg_up_h2v1(s[2], s[3], 1);
+        }
+      }
+    }
+  }
+  uint32_t p[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) p[k] = mjpg_bgr((int32_t)((yy >> (8 * k)) & 0xff), cv[0][k], cv[1][k]);
+  // 4 x 24 bits -> 3 dwords
+  uint3 o;
+  o.x = p[0] | (p[1] << 24);
+  o.y = (p[1] >> 8) | (p[2] << 16);
+  o.z = (p[2] >> 16) | (p[3] << 8);
+  *reinterpret_cast<uint3*>(bgr + (size_t)f * img_stride + ((size_t)y * W + x0) * 3) = o;
 }
 
 // coef: nframes coefficient streams `slot` bytes apart; out: nframes GRAY8 planes
@@ -5491,6 +5594,20 @@ hipError_t launch_mjpg_idct(const uint8_t* coef, size_t slot, uint8_t* out, size
   const uint32_t nb = (uint32_t)(W / 8) * (uint32_t)(H / 8);
   hipLaunchKernelGGL(k_mjpg_idct, dim3((nb + kMjpgBlocksPerWg - 1) / kMjpgBlocksPerWg, nframes), dim3(256), 0, st,
                      coef, slot, out, out_stride, W, W / 8, nb);
+  return hipGetLastError();
+}
+
+// colour on, after launch_mjpg_idct on the same stream: the chroma planes
+// (planes: [nframes][2] planes plane_stride >= W * H bytes apart) and the BGR8 images
+// (bgr: nframes images img_stride bytes apart, like the gray planes in `gray`)
+hipError_t launch_mjpg_color(const uint8_t* coef, size_t slot, const uint8_t* gray, uint8_t* planes,
+                             size_t plane_stride, uint8_t* bgr, size_t img_stride, int W, int H, int nframes,
+                             hipStream_t st) {
+  const uint32_t nb = (uint32_t)(W / 8) * (uint32_t)(H / 8);
+  hipLaunchKernelGGL(k_mjpg_idct_chroma, dim3((nb + kMjpgBlocksPerWg - 1) / kMjpgBlocksPerWg, nframes, 2), dim3(256),
+                     0, st, coef, slot, planes, plane_stride, nb);
+  hipLaunchKernelGGL(k_mjpg_bgr, dim3((W / 4 + 63) / 64, (H + 3) / 4, nframes), dim3(64, 4), 0, st, coef, slot, gray,
+                     planes, plane_stride, bgr, img_stride, W, H);
   return hipGetLastError();
 }
 

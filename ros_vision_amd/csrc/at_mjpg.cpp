@@ -165,10 +165,12 @@ uint32_t MjpgDecoder::decode_index(int bx, int by) const {
   return (uint32_t)(((my * mcux + mx) * vs + by % vs) * hs + bx % hs);
 }
 
-int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h) {
+int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h, bool keep_chroma) {
   info_ = MjpgInfo{};
   bw_ = bh_ = gw_ = gh_ = 0;
   kept_tokens_ = 0;
+  chroma_ = false;
+  cbw_ = cbh_ = 0;
   if (!jpg || len < 4 || jpg[0] != 0xff || jpg[1] != 0xd8) return kMjpgInvalid;
   uint8_t qt[4][64];
   bool qt_def[4] = {false, false, false, false};
@@ -282,6 +284,13 @@ int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h) 
     }
   }
   for (int k = 0; k < 64; k++) q_[kZigzag[k]] = qt[comp[0].tq][k];
+  const bool chroma = keep_chroma && info_.ncomp == 3;
+  if (chroma)
+    for (int c = 0; c < 2; c++) {
+      // each component its own table: Cb and Cr may name different ones
+      if (!qt_def[comp[c + 1].tq]) return kMjpgInvalid;
+      for (int k = 0; k < 64; k++) cq_[c][kZigzag[k]] = qt[comp[c + 1].tq][k];
+    }
 
   const int hs = info_.hs, vs = info_.vs;
   bw_ = (info_.width + 7) / 8;
@@ -294,6 +303,14 @@ int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h) 
   // decoded, never with what a header merely claims)
   tok_.clear();
   start_.clear();
+  for (int c = 0; c < 2; c++) {
+    ctok_[c].clear();
+    cstart_[c].clear();
+  }
+  // where each component's tokens go: luma always, chroma only with colour on
+  std::vector<uint32_t>* const tokv[3] = {&tok_, chroma ? &ctok_[0] : nullptr, chroma ? &ctok_[1] : nullptr};
+  std::vector<uint32_t>* const startv[3] = {&start_, chroma ? &cstart_[0] : nullptr,
+                                            chroma ? &cstart_[1] : nullptr};
 
   BitReader br(jpg, len, pos);
   int pred[3] = {0, 0, 0};
@@ -316,13 +333,14 @@ int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h) 
       const int ci = b < hs * vs ? 0 : b - hs * vs + 1;
       const Huff& hd = dc[comp[ci].td];
       const Huff& ha = ac[comp[ci].ta];
-      const bool keep = ci == 0;
-      if (keep) start_.push_back((uint32_t)tok_.size());
+      std::vector<uint32_t>* const tk = tokv[ci];
+      const bool keep = tk != nullptr;
+      if (keep) startv[ci]->push_back((uint32_t)tk->size());
       const int t = huff_decode(br, hd);
       if (t < 0 || t > 15) return kMjpgInvalid;
       if (t) pred[ci] += receive_extend(br, t);
       pred[ci] = (int16_t)pred[ci];  // a coefficient is 16 bits (corrupt streams only get here)
-      if (keep && pred[0]) tok_.push_back((uint32_t)(uint16_t)pred[0]);
+      if (keep && pred[ci]) tk->push_back((uint32_t)(uint16_t)pred[ci]);
       for (int k = 1; k < 64;) {
         const int rs = huff_decode(br, ha);
         if (rs < 0) return kMjpgInvalid;
@@ -335,7 +353,7 @@ int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h) 
         k += r;
         if (k > 63) return kMjpgInvalid;
         const int v = receive_extend(br, sz);
-        if (keep) tok_.push_back(((uint32_t)k << 16) | (uint32_t)(uint16_t)v);
+        if (keep) tk->push_back(((uint32_t)k << 16) | (uint32_t)(uint16_t)v);
         k++;
       }
     }
@@ -343,6 +361,16 @@ int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h) 
   }
   start_.push_back((uint32_t)tok_.size());
   if (start_.size() != nluma + 1) return kMjpgInvalid;
+  if (chroma) {
+    // one block of each chroma component per MCU: the chroma grid is the MCU grid
+    for (int c = 0; c < 2; c++) {
+      cstart_[c].push_back((uint32_t)ctok_[c].size());
+      if (cstart_[c].size() != (size_t)nmcu + 1) return kMjpgInvalid;
+    }
+    cbw_ = mcux;
+    cbh_ = mcuy;
+  }
+  chroma_ = keep_chroma;
   uint32_t kept = 0;
   if (gw_ == bw_ && gh_ == bh_) {
     kept = (uint32_t)tok_.size();
@@ -357,23 +385,45 @@ int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h) 
   return kMjpgOk;
 }
 
-bool MjpgDecoder::dense() const {
-  const size_t nb = nblocks();
-  return 4 * (nb + 1) + 4 * (size_t)kept_tokens_ >= 128 * nb;
+MjpgDecoder::Plane MjpgDecoder::plane(int c) const {
+  if (c == 0) return Plane{q_, tok_.data(), start_.data(), bw_, bh_, kept_tokens_, true};
+  const std::vector<uint32_t>& st = cstart_[c - 1];
+  return Plane{cq_[c - 1], ctok_[c - 1].data(), st.data(), cbw_, cbh_, st.empty() ? 0u : st.back(), false};
 }
+
+bool MjpgDecoder::plane_dense(const Plane& p) {
+  const size_t nb = (size_t)p.bw * p.bh;
+  return 4 * (nb + 1) + 4 * (size_t)p.kept >= 128 * nb;
+}
+
+size_t MjpgDecoder::plane_bytes(const Plane& p) {
+  const size_t nb = (size_t)p.bw * p.bh;
+  return (size_t)kMjpgHdrBytes + (plane_dense(p) ? 128 * nb : 4 * (nb + 1) + 4 * (size_t)p.kept);
+}
+
+bool MjpgDecoder::dense() const { return plane_dense(plane(0)); }
+
+static size_t sub_align(size_t n) { return (n + kMjpgSubAlign - 1) & ~(size_t)(kMjpgSubAlign - 1); }
 
 size_t MjpgDecoder::packed_bytes() const {
-  const size_t nb = nblocks();
-  return (size_t)kMjpgHdrBytes + (dense() ? 128 * nb : 4 * (nb + 1) + 4 * (size_t)kept_tokens_);
+  size_t n = plane_bytes(plane(0));
+  if (chroma_ && cbw_)
+    for (int c = 1; c < 3; c++) n = sub_align(n) + plane_bytes(plane(c));
+  return n;
 }
 
-int MjpgDecoder::pack(uint8_t* dst, size_t cap) const {
-  const uint32_t nb = nblocks();
-  if (!dst || !nb || start_.size() != (size_t)gw_ * gh_ + 1 || cap < packed_bytes()) return kMjpgInvalid;
-  const bool dn = dense();
+size_t MjpgDecoder::slot_bytes(int w, int h, bool color) {
+  const size_t one = (size_t)kMjpgHdrBytes + 128 * (size_t)((w + 7) / 8) * (size_t)((h + 7) / 8);
+  return color ? 3 * sub_align(one) : one;
+}
+
+// header (q, mode, token count, block count) and payload of one plane
+void MjpgDecoder::pack_plane(const Plane& p, uint8_t* dst) const {
+  const uint32_t nb = (uint32_t)(p.bw * p.bh);
+  const bool dn = plane_dense(p);
   memset(dst, 0, kMjpgHdrBytes);
-  memcpy(dst, q_, sizeof(q_));
-  const uint32_t mode = dn ? kMjpgDense : kMjpgSparse, ntok = dn ? 0 : kept_tokens_;
+  memcpy(dst, p.q, 64 * sizeof(uint16_t));
+  const uint32_t mode = dn ? kMjpgDense : kMjpgSparse, ntok = dn ? 0 : p.kept;
   memcpy(dst + kMjpgModeOff, &mode, 4);
   memcpy(dst + kMjpgNtokOff, &ntok, 4);
   memcpy(dst + kMjpgNblkOff, &nb, 4);
@@ -382,39 +432,62 @@ int MjpgDecoder::pack(uint8_t* dst, size_t cap) const {
     memset(pay, 0, (size_t)128 * nb);
     int16_t* out = reinterpret_cast<int16_t*>(pay);
     uint32_t b = 0;
-    for (int by = 0; by < bh_; by++)
-      for (int bx = 0; bx < bw_; bx++, b++) {
-        const uint32_t i = decode_index(bx, by);
-        for (uint32_t t = start_[i]; t < start_[i + 1]; t++)
-          out[(size_t)b * 64 + kZigzag[(tok_[t] >> 16) & 63]] = (int16_t)(uint16_t)(tok_[t] & 0xffffu);
+    for (int by = 0; by < p.bh; by++)
+      for (int bx = 0; bx < p.bw; bx++, b++) {
+        const uint32_t i = block_index(p, bx, by);
+        for (uint32_t t = p.start[i]; t < p.start[i + 1]; t++)
+          out[(size_t)b * 64 + kZigzag[(p.tok[t] >> 16) & 63]] = (int16_t)(uint16_t)(p.tok[t] & 0xffffu);
       }
-    return kMjpgOk;
+    return;
   }
   uint32_t* off = reinterpret_cast<uint32_t*>(pay);
   uint32_t* tk = off + nb + 1;
   uint32_t o = 0, b = 0;
-  for (int by = 0; by < bh_; by++)
-    for (int bx = 0; bx < bw_; bx++, b++) {
-      const uint32_t i = decode_index(bx, by);
-      const uint32_t n = start_[i + 1] - start_[i];
+  for (int by = 0; by < p.bh; by++)
+    for (int bx = 0; bx < p.bw; bx++, b++) {
+      const uint32_t i = block_index(p, bx, by);
+      const uint32_t n = p.start[i + 1] - p.start[i];
       off[b] = o;
-      if (n) memcpy(tk + o, tok_.data() + start_[i], (size_t)n * 4);
+      if (n) memcpy(tk + o, p.tok + p.start[i], (size_t)n * 4);
       o += n;
     }
   off[nb] = o;
+}
+
+int MjpgDecoder::pack(uint8_t* dst, size_t cap) const {
+  const uint32_t nb = nblocks();
+  if (!dst || !nb || start_.size() != (size_t)gw_ * gh_ + 1 || cap < packed_bytes()) return kMjpgInvalid;
+  pack_plane(plane(0), dst);
+  if (!chroma_) return kMjpgOk;
+  // colour on: the sampling word, then the chroma sub-streams behind the luma stream
+  const uint32_t samp = (uint32_t)info_.hs | ((uint32_t)info_.vs << 8) | ((uint32_t)info_.ncomp << 16);
+  memcpy(dst + kMjpgSampOff, &samp, 4);
+  if (!cbw_) return kMjpgOk;  // a single-component frame: no sub-streams, offsets 0
+  size_t at = plane_bytes(plane(0));
+  for (int c = 1; c < 3; c++) {
+    const Plane p = plane(c);
+    if (cstart_[c - 1].size() != (size_t)cbw_ * cbh_ + 1) return kMjpgInvalid;
+    const size_t sub = sub_align(at);
+    memset(dst + at, 0, sub - at);
+    pack_plane(p, dst + sub);
+    const uint32_t off32 = (uint32_t)sub, bw = (uint32_t)cbw_, hs = (uint32_t)info_.hs, vs = (uint32_t)info_.vs;
+    memcpy(dst + (c == 1 ? kMjpgCbOff : kMjpgCrOff), &off32, 4);
+    memcpy(dst + sub + kMjpgBwOff, &bw, 4);
+    memcpy(dst + sub + kMjpgHsOff, &hs, 4);
+    memcpy(dst + sub + kMjpgVsOff, &vs, 4);
+    at = sub + plane_bytes(p);
+  }
   return kMjpgOk;
 }
 
-int MjpgDecoder::to_gray(uint8_t* gray, size_t cap) const {
-  const int W = info_.width, H = info_.height;
-  if (!gray || !nblocks() || start_.size() != (size_t)gw_ * gh_ + 1 || cap < (size_t)W * H) return kMjpgInvalid;
-  for (int by = 0; by < bh_; by++)
-    for (int bx = 0; bx < bw_; bx++) {
+void MjpgDecoder::idct_plane(const Plane& p, uint8_t* out, size_t stride, int w, int h) const {
+  for (int by = 0; by < p.bh; by++)
+    for (int bx = 0; bx < p.bw; bx++) {
       int32_t ws[64] = {0};
-      const uint32_t i = decode_index(bx, by);
-      for (uint32_t t = start_[i]; t < start_[i + 1]; t++) {
-        const int nat = kZigzag[(tok_[t] >> 16) & 63];
-        ws[nat] = (int32_t)(int16_t)(uint16_t)(tok_[t] & 0xffffu) * (int32_t)q_[nat];
+      const uint32_t i = block_index(p, bx, by);
+      for (uint32_t t = p.start[i]; t < p.start[i + 1]; t++) {
+        const int nat = kZigzag[(p.tok[t] >> 16) & 63];
+        ws[nat] = (int32_t)(int16_t)(uint16_t)(p.tok[t] & 0xffffu) * (int32_t)p.q[nat];
       }
       for (int c = 0; c < 8; c++) {
         int32_t v[8];
@@ -424,13 +497,70 @@ int MjpgDecoder::to_gray(uint8_t* gray, size_t cap) const {
       }
       for (int r = 0; r < 8; r++) {
         const int y = by * 8 + r;
-        if (y >= H) break;
+        if (y >= h) break;
         int32_t v[8];
         for (int c = 0; c < 8; c++) v[c] = ws[r * 8 + c];
         mjpg_idct_1d<18>(v);
-        for (int c = 0; c < 8 && bx * 8 + c < W; c++) gray[(size_t)y * W + bx * 8 + c] = (uint8_t)mjpg_pixel(v[c]);
+        for (int c = 0; c < 8 && bx * 8 + c < w; c++) out[(size_t)y * stride + bx * 8 + c] = (uint8_t)mjpg_pixel(v[c]);
       }
     }
+}
+
+int MjpgDecoder::to_gray(uint8_t* gray, size_t cap) const {
+  const int W = info_.width, H = info_.height;
+  if (!gray || !nblocks() || start_.size() != (size_t)gw_ * gh_ + 1 || cap < (size_t)W * H) return kMjpgInvalid;
+  idct_plane(plane(0), gray, (size_t)W, W, H);
+  return kMjpgOk;
+}
+
+int MjpgDecoder::to_bgr(uint8_t* bgr, size_t cap) const {
+  const int W = info_.width, H = info_.height;
+  if (!bgr || !nblocks() || !chroma_ || start_.size() != (size_t)gw_ * gh_ + 1 || cap < (size_t)W * H * 3)
+    return kMjpgInvalid;
+  std::vector<uint8_t> y((size_t)W * H);
+  idct_plane(plane(0), y.data(), (size_t)W, W, H);
+  if (!cbw_) {
+    for (size_t i = 0; i < y.size(); i++) bgr[3 * i] = bgr[3 * i + 1] = bgr[3 * i + 2] = y[i];
+    return kMjpgOk;
+  }
+  const int hs = info_.hs, vs = info_.vs;
+  const int cw = (W + hs - 1) / hs, ch = (H + vs - 1) / vs;  // the real chroma samples
+  if (cw > cbw_ * 8 || ch > cbh_ * 8) return kMjpgInvalid;
+  std::vector<uint8_t> cc[2];
+  for (int c = 0; c < 2; c++) {
+    if (cstart_[c].size() != (size_t)cbw_ * cbh_ + 1) return kMjpgInvalid;
+    cc[c].resize((size_t)cw * ch);
+    idct_plane(plane(c + 1), cc[c].data(), (size_t)cw, cw, ch);
+  }
+  for (int py = 0; py < H; py++) {
+    // vertical neighbour of a 4:2:0 row: above for the even output row, below for the
+    // odd one, the first / last real chroma row replicated
+    const int j = py / vs, k = py & 1;
+    const int n = k ? (j + 1 < ch ? j + 1 : ch - 1) : (j > 0 ? j - 1 : 0);
+    for (int px = 0; px < W; px++) {
+      int32_t v[2];
+      for (int c = 0; c < 2; c++) {
+        const uint8_t* a = cc[c].data() + (size_t)j * cw;
+        if (hs == 1) {
+          v[c] = a[px];
+          continue;
+        }
+        const int i = px >> 1, odd = px & 1;
+        const int nb = odd ? (i + 1 < cw ? i + 1 : cw - 1) : (i > 0 ? i - 1 : 0);
+        if (vs == 1) {
+          v[c] = mjpg_up_h2v1(a[i], a[nb], odd);
+        } else {
+          const uint8_t* an = cc[c].data() + (size_t)n * cw;
+          v[c] = mjpg_up_h2v2(3 * a[i] + an[i], 3 * a[nb] + an[nb], odd);
+        }
+      }
+      const uint32_t p = mjpg_bgr(y[(size_t)py * W + px], v[0], v[1]);
+      uint8_t* o = bgr + ((size_t)py * W + px) * 3;
+      o[0] = (uint8_t)p;
+      o[1] = (uint8_t)(p >> 8);
+      o[2] = (uint8_t)(p >> 16);
+    }
+  }
   return kMjpgOk;
 }
 
@@ -446,6 +576,17 @@ extern "C" int at_mjpg_decode_gray_host(const uint8_t* jpg, size_t len, uint8_t*
   if (h) *h = dec.info().height;
   if (rc != at::kMjpgOk || !gray) return rc;
   return dec.to_gray(gray, cap);
+}
+
+extern "C" int at_mjpg_decode_bgr_host(const uint8_t* jpg, size_t len, uint8_t* bgr, size_t cap, int* w, int* h) {
+  at::MjpgDecoder dec;
+  if (w) *w = 0;
+  if (h) *h = 0;
+  const int rc = dec.decode(jpg, len, bgr ? 0 : -1, 0, true);
+  if (w) *w = dec.info().width;
+  if (h) *h = dec.info().height;
+  if (rc != at::kMjpgOk || !bgr) return rc;
+  return dec.to_bgr(bgr, cap);
 }
 
 extern "C" int at_mjpg_stream_mode_host(const uint8_t* jpg, size_t len, int want_w, int want_h,

@@ -6,6 +6,9 @@
 // prediction and restart handling.  Only the luma coefficients are kept (AprilTag
 // detection reads luma); they go to the GPU still quantised, where k_mjpg_idct
 // (at_kernels.hip) dequantises, runs the inverse DCT and writes the GRAY8 plane.
+// With colour on (decode(..., keep_chroma), at_mjpg_set_color) the Cb and Cr
+// coefficients are kept too and travel as two more sub-streams behind the luma
+// one; k_mjpg_idct_chroma and k_mjpg_bgr then produce the BGR8 image.
 //
 // Plain C++17, no HIP include: compiles alone with the host compiler (the
 // sanitized stand-alone check tests/mjpg_host_check.cpp builds it that way).
@@ -25,6 +28,17 @@
 // prediction and dropped here, so the stream holds exactly the visible blocks.
 // Dense is chosen whenever sparse would not be smaller, so the payload never
 // exceeds 128 B per block (2 B per pixel) and no frame can fail for size.
+//
+// Colour on: the luma header also carries
+//     u32 cb_off, cr_off   byte offsets of the Cb / Cr sub-streams from the start of the
+//                          frame's stream (multiples of 16; 0: a single-component frame)
+//     u32 sampling         hs | vs << 8 | ncomp << 16
+// and each chroma sub-stream is a header of the same kMjpgHdrBytes (the component's own
+// q[64], mode, ntokens, nblocks, then u32 bw: the plane's width in blocks, u32 hs, u32 vs)
+// followed by a sparse or dense payload chosen by the same rule.  A chroma plane is
+// cw = ceil(W / hs) by ch = ceil(H / vs) samples on a grid of ceil(cw / 8) x ceil(ch / 8)
+// blocks, which is the MCU grid: chroma has no padding blocks to drop.  With colour off
+// those header bytes are zero and nothing follows the luma payload, as before.
 #ifndef AT_MJPG_H_
 #define AT_MJPG_H_
 
@@ -44,6 +58,11 @@ namespace at {
 constexpr int kMjpgHdrBytes = 256;
 constexpr uint32_t kMjpgSparse = 0, kMjpgDense = 1;
 constexpr int kMjpgModeOff = 128, kMjpgNtokOff = 132, kMjpgNblkOff = 136;
+// colour on, luma header: the sub-streams' offsets and the sampling word
+constexpr int kMjpgCbOff = 140, kMjpgCrOff = 144, kMjpgSampOff = 148;
+// chroma sub-stream header: plane width in blocks, the frame's sampling factors
+constexpr int kMjpgBwOff = 140, kMjpgHsOff = 144, kMjpgVsOff = 148;
+constexpr int kMjpgSubAlign = 16;  // a dense payload is read in 16-byte words
 
 // error codes of include/at_api.h (this header stands alone)
 constexpr int kMjpgOk = 0, kMjpgInvalid = -1, kMjpgUnsupported = -6;
@@ -107,6 +126,28 @@ AT_MJPG_HD uint32_t mjpg_pixel(int32_t v) {
   return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
+// libjpeg's "fancy" (triangle filter) chroma upsampling, one output sample.  `a` is
+// the nearer chroma sample, `nb` its neighbour on the output sample's side (the sample
+// itself at the picture's edge), `odd` the output column's parity.
+// 4:2:2 (h2v1): a and nb are samples of one chroma row.
+AT_MJPG_HD int32_t mjpg_up_h2v1(int32_t a, int32_t nb, int odd) { return (3 * a + nb + (odd ? 2 : 1)) >> 2; }
+// 4:2:0 (h2v2): a and nb are column sums s = 3 * (nearer row) + (farther row).
+AT_MJPG_HD int32_t mjpg_up_h2v2(int32_t a, int32_t nb, int odd) { return (3 * a + nb + (odd ? 7 : 8)) >> 4; }
+
+// libjpeg's YCbCr -> RGB (jdcolor.c: 16-bit fixed point, arithmetic shifts), packed
+// B | G << 8 | R << 16.  y, cb, cr in 0..255.
+AT_MJPG_HD uint32_t mjpg_bgr(int32_t y, int32_t cb, int32_t cr) {
+  cb -= 128;
+  cr -= 128;
+  int32_t r = y + ((91881 * cr + 32768) >> 16);                 // FIX(1.40200)
+  int32_t b = y + ((116130 * cb + 32768) >> 16);                // FIX(1.77200)
+  int32_t g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16);   // FIX(0.34414), FIX(0.71414)
+  r = r < 0 ? 0 : (r > 255 ? 255 : r);
+  g = g < 0 ? 0 : (g > 255 ? 255 : g);
+  b = b < 0 ? 0 : (b > 255 ? 255 : b);
+  return (uint32_t)b | ((uint32_t)g << 8) | ((uint32_t)r << 16);
+}
+
 // What the marker parser found.
 struct MjpgInfo {
   int width, height;
@@ -124,17 +165,28 @@ class MjpgDecoder {
   // Parses and entropy-decodes one JPEG.  want_w / want_h > 0: the picture must
   // have exactly that size (kMjpgInvalid otherwise).  On success the luma tokens
   // are held in this object until the next call; info() describes the stream.
-  int decode(const uint8_t* jpg, size_t len, int want_w, int want_h);
+  // keep_chroma: the Cb and Cr tokens of a three-component stream are held too, with
+  // each component's quantisation table (colour on); pack() then appends them.
+  int decode(const uint8_t* jpg, size_t len, int want_w, int want_h, bool keep_chroma = false);
   const MjpgInfo& info() const { return info_; }
   uint32_t nblocks() const { return (uint32_t)(bw_ * bh_); }
-  // bytes pack() writes (header + payload in the smaller encoding)
+  // chroma plane: blocks (0 unless chroma was kept), width in blocks
+  uint32_t chroma_nblocks() const { return (uint32_t)(cbw_ * cbh_); }
+  // bytes pack() writes (header + payload in the smaller encoding; colour on: the
+  // chroma sub-streams and the alignment in front of them too)
   size_t packed_bytes() const;
-  bool dense() const;
+  bool dense() const;  // the luma stream's encoding
   // Writes the coefficient stream of the decoded frame to dst (cap bytes, at least
-  // packed_bytes(); kMjpgHdrBytes + 128 * nblocks() always suffices).
+  // packed_bytes(); slot_bytes() of the picture's size always suffices).
   int pack(uint8_t* dst, size_t cap) const;
+  // The most a frame of w x h pixels can take (every plane dense; colour: 4:4:4).
+  static size_t slot_bytes(int w, int h, bool color);
   // Full host decode: the luma plane (width x height) through the same integer IDCT.
   int to_gray(uint8_t* gray, size_t cap) const;
+  // Full host decode to BGR8 [height][width][3] (after decode(..., keep_chroma = true)):
+  // chroma IDCT, fancy upsampling and colour conversion as libjpeg does them; a
+  // single-component stream gives B = G = R = Y.
+  int to_bgr(uint8_t* bgr, size_t cap) const;
 
  private:
   MjpgInfo info_{};
@@ -144,7 +196,31 @@ class MjpgDecoder {
   std::vector<uint32_t> tok_;        // tokens in decode order
   std::vector<uint32_t> start_;      // first token of each decoded block (decode order), + end
   uint32_t kept_tokens_ = 0;         // tokens of the visible blocks
+  bool chroma_ = false;              // the last decode kept chroma (colour on)
+  int cbw_ = 0, cbh_ = 0;            // chroma block grid (the MCU grid); 0 x 0 without chroma
+  uint16_t cq_[2][64] = {{0}};       // Cb / Cr quantisation tables, natural order
+  std::vector<uint32_t> ctok_[2];    // Cb / Cr tokens, blocks in raster (= decode) order
+  std::vector<uint32_t> cstart_[2];  // first token of each chroma block, + end
   uint32_t decode_index(int bx, int by) const;
+  // one plane's stream: the blocks of a bw x bh grid, block (bx, by) owning the tokens
+  // start[i] .. start[i + 1] with i = decode_index (luma) or raster (chroma)
+  struct Plane {
+    const uint16_t* q;
+    const uint32_t* tok;
+    const uint32_t* start;
+    int bw, bh;
+    uint32_t kept;
+    bool luma;
+  };
+  Plane plane(int c) const;  // 0 luma, 1 Cb, 2 Cr
+  uint32_t block_index(const Plane& p, int bx, int by) const {
+    return p.luma ? decode_index(bx, by) : (uint32_t)(by * p.bw + bx);
+  }
+  static bool plane_dense(const Plane& p);
+  static size_t plane_bytes(const Plane& p);
+  void pack_plane(const Plane& p, uint8_t* dst) const;
+  // IDCT of the plane's blocks into out (row stride `stride`), cropped to w x h
+  void idct_plane(const Plane& p, uint8_t* out, size_t stride, int w, int h) const;
 };
 
 }  // namespace at
@@ -153,6 +229,8 @@ class MjpgDecoder {
 // reference of the tests).  Returns 0 or a negative AT_E* code; *w / *h receive the
 // picture size as soon as the frame header has been parsed.
 extern "C" int at_mjpg_decode_gray_host(const uint8_t* jpg, size_t len, uint8_t* gray, size_t cap, int* w, int* h);
+// the same for the colour image: BGR8 [h][w][3], cap >= 3 * w * h (bgr == NULL: header only)
+extern "C" int at_mjpg_decode_bgr_host(const uint8_t* jpg, size_t len, uint8_t* bgr, size_t cap, int* w, int* h);
 // which encoding a frame of this stream takes on the link to a want_w x want_h detector
 // (0 x 0: any size): 0 sparse, 1 dense, < 0 the error at_enqueue_mjpg would give
 extern "C" int at_mjpg_stream_mode_host(const uint8_t* jpg, size_t len, int want_w, int want_h,

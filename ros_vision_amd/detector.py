@@ -37,6 +37,7 @@ EXPORTS = [
     "at_kernel_span", "at_host_alloc", "at_host_free",
     "at_enqueue_mjpg", "at_detect_mjpg", "at_detect_mjpg_batch", "at_mjpg_set_threads", "at_mjpg_stats",
     "at_mjpg_decode_gray_host", "at_mjpg_stream_mode_host",
+    "at_mjpg_set_color", "at_mjpg_bgr", "at_mjpg_copy_bgr", "at_mjpg_decode_bgr_host",
 ]
 
 TAG_SIZE = 0.1651  # metres, apriltags_cuda_detector.hpp:39
@@ -210,6 +211,12 @@ def load_library(path: str = LIB_PATH):
         L.at_mjpg_decode_gray_host.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
                                                C.POINTER(C.c_int)]
         L.at_mjpg_stream_mode_host.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    if hasattr(L, "at_mjpg_set_color"):  # (A/B builds of older sources lack the colour path)
+        L.at_mjpg_set_color.argtypes = [C.c_void_p, C.c_int]
+        L.at_mjpg_bgr.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.at_mjpg_copy_bgr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        L.at_mjpg_decode_bgr_host.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
+                                              C.POINTER(C.c_int)]
     _LIB = L
     return L
 
@@ -237,6 +244,23 @@ def mjpg_decode_gray(jpg: bytes):
     rc = L.at_mjpg_decode_gray_host(jpg, len(jpg), out.ctypes.data, out.size, C.byref(w), C.byref(h))
     if rc < 0:
         raise MjpgError("at_mjpg_decode_gray_host", rc)
+    return out
+
+
+def mjpg_decode_bgr(jpg: bytes):
+    """at_mjpg_decode_bgr_host: the BGR8 image (H, W, 3) uint8 of one baseline JPEG, decoded
+    on the host with the arithmetic the colour kernels run (no device needed): libjpeg's
+    integer IDCT, fancy upsampling and colour conversion."""
+    L = load_library()
+    jpg = bytes(jpg)
+    w, h = C.c_int(), C.c_int()
+    rc = L.at_mjpg_decode_bgr_host(jpg, len(jpg), None, 0, C.byref(w), C.byref(h))
+    if rc < 0:
+        raise MjpgError("at_mjpg_decode_bgr_host", rc)
+    out = np.empty((h.value, w.value, 3), np.uint8)
+    rc = L.at_mjpg_decode_bgr_host(jpg, len(jpg), out.ctypes.data, out.size, C.byref(w), C.byref(h))
+    if rc < 0:
+        raise MjpgError("at_mjpg_decode_bgr_host", rc)
     return out
 
 
@@ -472,7 +496,28 @@ class GpuDetector:
         """Host threads decoding the frames of one MJPG batch (1..16, default 1)."""
         _check(load_library().at_mjpg_set_threads(self._h, int(n)), "at_mjpg_set_threads")
 
-    MJPG_STATS = ("compressed_bytes", "device_bytes", "dense_frames", "host_decode_us", "idct_kernel_ns")
+    def set_mjpg_color(self, on=True):
+        """at_mjpg_set_color: from the next MJPG batch on, also decode chroma and produce each
+        frame's BGR8 image on the GPU (copy_bgr, mjpg_bgr_ptr, annotate_staged, the
+        game-piece tensors).  Off by default."""
+        _check(load_library().at_mjpg_set_color(self._h, int(bool(on))), "at_mjpg_set_color")
+
+    def mjpg_bgr_ptr(self, frame=0):
+        """at_mjpg_bgr: device pointer of frame `frame`'s BGR8 image of the last (colour-on
+        MJPG) batch, valid until the next batch."""
+        ptr = C.c_void_p()
+        _check(load_library().at_mjpg_bgr(self._h, frame, C.byref(ptr)), "at_mjpg_bgr")
+        return ptr.value
+
+    def copy_bgr(self, frame=0):
+        """at_mjpg_copy_bgr: host copy (H, W, 3) uint8 of that image; raises unless the last
+        batch was an MJPG batch enqueued with colour on."""
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        _check(load_library().at_mjpg_copy_bgr(self._h, frame, out.ctypes.data, out.size), "at_mjpg_copy_bgr")
+        return out
+
+    MJPG_STATS = ("compressed_bytes", "device_bytes", "dense_frames", "host_decode_us", "idct_kernel_ns",
+                  "color_kernels_ns")
 
     def mjpg_stats(self):
         """at_mjpg_stats of the last MJPG batch."""
@@ -573,7 +618,8 @@ class GpuDetector:
 
     def annotate_staged(self, frame=0):
         """at_annotate_staged: the annotated image of host BGR8 frame `frame` of the last
-        batch, drawn on its staged copy in HBM; returns it (H, W, 3) uint8."""
+        batch, drawn on its staged copy in HBM (after a colour-on MJPG batch: on the
+        decoded image); returns it (H, W, 3) uint8."""
         arr, n = self._records_array(frame)
         out = np.empty((self.height, self.width, 3), np.uint8)
         _check(load_library().at_annotate_staged(self._h, frame, arr, n, out.ctypes.data), "at_annotate_staged")

@@ -125,7 +125,7 @@ class ApriltagsDetectorNode:
     """ApriltagsDetector (apriltags_cuda_detector.cu) without the ROS transport."""
 
     def __init__(self, width, height, parameters=None, calibration_dir=None, system_config_path=None,
-                 publishers=None, device=0):
+                 publishers=None, device=0, mjpg_color=False):
         self.params = dict(PARAMETER_DEFAULTS)
         self.params.update(parameters or {})
         serial = self.params["camera_serial"]
@@ -138,6 +138,10 @@ class ApriltagsDetectorNode:
         self.extrinsic_rotation, self.extrinsic_offset, self.location = (
             load_extrinsics(system_config_path, serial) if system_config_path else (np.eye(3), np.zeros(3), None))
         self.detector = GpuDetector(width, height, cam, dist, device=device, tag_size=TAG_SIZE)
+        # "jpeg" frames: also decode colour on the GPU and publish the annotated image
+        self.mjpg_color = bool(mjpg_color)
+        if self.mjpg_color:
+            self.detector.set_mjpg_color(True)
         self.publishers = publishers or {}
         self.pose_topic = self.params["publish_pose_to_topic"]
         self.camera_pose_topic = self.pose_topic + "_camera"
@@ -164,8 +168,10 @@ class ApriltagsDetectorNode:
         """One frame: `image` is bgr8 [H, W, 3] (what cv_bridge hands the reference),
         yuyv [H, 2W], mono8 [H, W], or -- encoding "jpeg" -- the bytes of one MJPG camera
         frame (a sensor_msgs/CompressedImage's data): its luma is decoded on the way to
-        the GPU, poses and tables come out as for the other encodings, and no annotated
-        image is published (there is no colour image to draw on)."""
+        the GPU, poses and tables come out as for the other encodings.  An annotated
+        image is published for it only with mjpg_color=True: the frame's colour is then
+        decoded on the GPU too and outlined there (at_annotate_staged); otherwise there is
+        no colour image to draw on."""
         start = time.perf_counter()
         latency_s = (receive_time_s if receive_time_s is not None else time.time()) - stamp_s
         det0 = time.perf_counter()
@@ -185,6 +191,8 @@ class ApriltagsDetectorNode:
             res.tag_detection_array.append((tag.id, rx, ry, rz))
         if encoding == "bgr8":
             res.image = draw_detection_outlines(np.array(image, copy=True), dets)
+        elif encoding == "jpeg" and self.mjpg_color:
+            res.image = self.detector.annotate_staged(0)
         nt0 = time.perf_counter()
         self._publish("networktables", res.networktables_pose_data)
         self._publish("networktables_proto", res.proto_tags)

@@ -8,6 +8,11 @@ through the same round-robin loop over the same detector instances, so the two
 rates differ only by the input path.  Also reported: the host decode time per frame,
 k_mjpg_idct's time per batch and the bytes per frame that cross the link.
 
+A colour leg follows (at_mjpg_set_color): the same boards tinted, so that the chroma
+planes carry coefficients, through the same loop once with colour off and once with it
+on -- frames/s, link bytes per frame, and the time of the two colour kernels
+(k_mjpg_idct_chroma + k_mjpg_bgr) per batch.
+
 Writes one JSON file (default profiles/mjpg_bench.json) and prints it.
 
   python tools/mjpg_bench.py [--batch 32] [--instances 4] [--steps 24] [--threads 1,4,16]
@@ -126,6 +131,51 @@ def main():
     ns = sorted(ns[2:])
     res["k_mjpg_idct_ms_per_batch"] = {"median": round(ns[len(ns) // 2] / 1e6, 4), "min": round(ns[0] / 1e6, 4),
                                        "frames": B, "how": "hipEventElapsedTime around the launch, 10 batches"}
+    # colour: tinted frames (real chroma), colour off and on through the same loop
+    tinted = []
+    yy, xx = np.mgrid[0:H, 0:W]
+    for f in yuyv:
+        g = np.ascontiguousarray(f[:, 0::2]).astype(np.int32)
+        rgb = np.stack([np.clip(g + 40 * np.sin(xx / 9.0), 0, 255), g, np.clip(g - 35 * np.cos(yy / 7.0), 0, 255)], -1)
+        b = io.BytesIO()
+        Image.fromarray(rgb.astype(np.uint8)).save(b, "JPEG", quality=args.quality, subsampling=1)
+        tinted.append(b.getvalue())
+    chk = rva.GpuDetector(W, H)
+    chk.set_mjpg_color(True)
+    chk.detect_mjpg(tinted[0])
+    want = np.asarray(Image.open(io.BytesIO(tinted[0])).convert("RGB"))[:, :, ::-1]
+    res["mjpg_color"] = {"image_equals_pillow": bool(np.array_equal(chk.copy_bgr(), want)), "legs": []}
+    chk.close()
+    nt = max(int(v) for v in args.threads.split(","))
+    for d in dets:
+        d.set_mjpg_threads(nt)
+    for color in (False, True):
+        for d in dets:
+            d.set_mjpg_color(color)
+        run_mjpg(dets, tinted, B, len(dets))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run_mjpg(dets, tinted, B, args.steps)
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        s = dets[0].mjpg_stats()
+        res["mjpg_color"]["legs"].append({
+            "color": color, "threads": nt, "frames_per_s": round(args.steps * B / el, 1),
+            "link_bytes_per_frame": round(s["device_bytes"] / B, 1),
+            "compressed_bytes_per_frame": round(s["compressed_bytes"] / B, 1),
+            "host_decode_ms_per_frame_wall": round(s["host_decode_us"] / 1e3 / B, 4)})
+    d = dets[0]
+    d.set_profiling(True)
+    ns = []
+    for i in range(12):
+        d.enqueue_mjpg([tinted[(i + j) % len(tinted)] for j in range(B)])
+        d.collect(counts_only=True)
+        ns.append(d.mjpg_stats()["color_kernels_ns"])
+    d.set_profiling(False)
+    ns = sorted(ns[2:])
+    res["mjpg_color"]["color_kernels_ms_per_batch"] = {
+        "median": round(ns[len(ns) // 2] / 1e6, 4), "min": round(ns[0] / 1e6, 4), "frames": B,
+        "how": "hipEventElapsedTime around k_mjpg_idct_chroma + k_mjpg_bgr, 10 batches"}
     for d in dets:
         d.close()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
