@@ -1547,39 +1547,33 @@ __device__ __forceinline__ uint32_t pair_hash(uint64_t key) {
   if (AT_BND_HASH32) return ((uint32_t)key * 0x9E3779B1u) >> 23;
   return (uint32_t)(mix_hash(key) & (kLdsPairSlots - 1));
 }
-__device__ __forceinline__ bool lds_pair_add(uint64_t* keys, uint32_t* cnts, uint64_t key, uint32_t len) {
+// adds `len` to the key's count; returns the slot counted into (kNoPairSlot: table full)
+constexpr uint32_t kNoPairSlot = 0xffffffffu;
+__device__ __forceinline__ uint32_t lds_pair_add(uint64_t* keys, uint32_t* cnts, uint64_t key, uint32_t len) {
   uint32_t h = pair_hash(key);
   for (int probe = 0; probe < kLdsPairSlots; probe++) {
     const uint64_t k = keys[h];
     if (k == key) {
       atomicAdd(cnts + h, len);
-      return true;
+      return h;
     }
     if (k == 0) {
       const uint64_t prev = atomicCAS((unsigned long long*)(keys + h), 0ull, (unsigned long long)key);
       if (prev == 0 || prev == key) {
         atomicAdd(cnts + h, len);
-        return true;
+        return h;
       }
     }
     h = (h + 1) & (kLdsPairSlots - 1);
   }
-  return false;
-}
-
-// slot of a key already in the tile's LDS pair table
-__device__ __forceinline__ uint32_t lds_pair_slot(const uint64_t* keys, uint64_t key) {
-  uint32_t h = pair_hash(key);
-  while (keys[h] != key) h = (h + 1) & (kLdsPairSlots - 1);
-  return h;
+  return kNoPairSlot;
 }
 
 // Narrow tile points (tcnt flag kTileNarrow): 4-B words, the tile's pair-entry
 // index (9 bits) over the point bits of the key -- x (10), y (10), b2w, dxy (2):
 // the labels are the entry's key (pent_key), so they need not travel per point.
-__device__ __forceinline__ uint32_t narrow_point(uint32_t entry, uint64_t key) {
-  return (entry << 23) | ((uint32_t)(key >> 1) & 0x7ffffcu) | ((uint32_t)key & 3u);
-}
+// k_boundary stages the same word with the pair's LDS table slot in the index field.
+__device__ __forceinline__ uint32_t narrow_xy(uint32_t x, uint32_t y) { return ((x & 0x3ff) << 13) | ((y & 0x3ff) << 3); }
 // ... and back to the low 24 key bits (x << 14 | y << 4 | b2w << 3 | dxy)
 __device__ __forceinline__ uint32_t narrow_bits(uint32_t w) { return ((w & 0x7ffffcu) << 1) | (w & 3u); }
 
@@ -1616,10 +1610,13 @@ template <bool KEPT>
 __global__ __launch_bounds__(256) AT_BND_ATTR void k_boundary(DevBufs b, Geom g) {
   __shared__ uint64_t s_pkey[kLdsPairSlots];
   __shared__ uint32_t s_pcnt[kLdsPairSlots];
-  // points staged in LDS up to kBndStage (typical tiles hold ~0.7 points per
-  // pixel); the rare denser tile writes the excess straight to its global
-  // region.  Keeping the stage small keeps 6 workgroups (24 waves) per CU.
-  __shared__ uint64_t s_pts[kBndStage];
+  // points staged in LDS as 4-B words (pair table slot << 23 | point bits), up to
+  // kBndStage = two per pixel: every tile of the camera stream fits (its densest
+  // hold ~1350 at 720p, ~1450 at 1080p; an eighth of them hold more than 1024).
+  // A tile with more (dense synthetic patterns) is crowded: it writes nothing from
+  // the stage and runs the rows a second time (below).  8 KB of stage keeps 6
+  // workgroups (24 waves) per CU.
+  __shared__ uint32_t s_pts[kBndStage];
   __shared__ uint32_t s_npts, s_nent, s_spill;
   // threshold values with pixels of blobs under 25 pixels folded to 127: every
   // BlobDiff condition then reads one byte per neighbour (v0 + v1 == 255 holds
@@ -1691,8 +1688,11 @@ __global__ __launch_bounds__(256) AT_BND_ATTR void k_boundary(DevBufs b, Geom g)
   // runs may continue from the upper row into the lower: only their counts are used.)
   const int cx = 2 * (int)(lane & 31);  // tile column of the lane's first pixel
   const int xa = 1 + bi.x * 64 + cx;    // its image column
-  for (int r = 0; r < kBndRows / 2; r++) {
-    const int ly = (r * 4 + threadIdx.y) * 2 + (int)(lane >> 5);  // tile row of the pixels
+  // the lane's points of step r: direction mask (bit 4j + dir for pixel j), own and
+  // neighbour labels, black-to-white flags; returns the pixels' image row
+  auto step_points = [&](int r, int wrow, uint32_t lane, int cx, int xa, uint32_t& hm, uint32_t (&nb)[8], uint32_t (&rep)[2],
+                         bool (&b2w)[2]) {
+    const int ly = (r * 4 + wrow) * 2 + (int)(lane >> 5);  // tile row of the pixels
     const int y = ty0 + ly;
     // threshold bytes of halo columns cx .. cx+3 (left neighbour, the two pixels, right
     // neighbour) in rows ly and ly + 1: four aligned 16-bit LDS reads
@@ -1701,9 +1701,7 @@ __global__ __launch_bounds__(256) AT_BND_ATTR void k_boundary(DevBufs b, Geom g)
                         ((uint32_t)*reinterpret_cast<const uint16_t*>(s_tthr + eb + 2) << 16);
     const uint32_t rb = (uint32_t)*reinterpret_cast<const uint16_t*>(s_tthr + eb + kTC) |
                         ((uint32_t)*reinterpret_cast<const uint16_t*>(s_tthr + eb + kTC + 2) << 16);
-    // the pixels' points: direction mask (bit 4j + dir for pixel j), neighbour labels
-    uint32_t hm = 0, nb[8], rep[2];
-    bool b2w[2];
+    hm = 0;
 #pragma unroll
     for (int j = 0; j < 2; j++) {
       rep[j] = 0;
@@ -1729,6 +1727,12 @@ __global__ __launch_bounds__(256) AT_BND_ATTR void k_boundary(DevBufs b, Geom g)
                           (!dedup && v0 + vdl == 255 ? 8u : 0u);
       hm |= pv ? pm << (4 * j) : 0u;
     }
+    return y;
+  };
+  for (int r = 0; r < kBndRows / 2; r++) {
+    uint32_t hm, nb[8], rep[2];
+    bool b2w[2];
+    const int y = step_points(r, (int)threadIdx.y, lane, cx, xa, hm, nb, rep, b2w);
     // pair histogram: the lane's first pair with the count of its points in it (labels
     // are < 2^20 -- decimated planes of at most 1024 x 1024 -- so label equality is
     // key equality), runs of equal first pairs in consecutive lanes summed (wave scan),
@@ -1752,52 +1756,61 @@ __global__ __launch_bounds__(256) AT_BND_ATTR void k_boundary(DevBufs b, Geom g)
     const uint32_t incl = sc & 0xffffu;
     const uint32_t below = (sc >> 16) - npts, wtot = wave_read(sc, 63) >> 16;
     const uint64_t kp = got ? make_qbp(rf, nf, 0, 0, 0, false) >> 24 : 0ull;
-    {
-      const uint64_t prev = wave_shr1_u64(kp);
-      const bool same = got && lane > 0 && prev == kp;
-      const uint64_t same_mask = __ballot(same);
-      const bool head = got && !same;
-      const uint32_t len = head ? run_len(same_mask, lane) : 1u;
-      const uint32_t incl_end = (uint32_t)__shfl((int)incl, (int)(lane + len - 1));
-      if (head) {
-        const uint32_t tot = incl_end - incl + cnt;
-        if (!lds_pair_add(s_pkey, s_pcnt, kp, tot)) {  // LDS table full
-          bnd_spill(b, f, kp, tot);
-          s_spill = 1;
-        }
-      }
-      if (__ballot(xm != 0)) {
-#pragma unroll
-        for (int d = 0; d < 8; d++) {
-          if ((xm >> d) & 1) {
-            const uint64_t k = make_qbp(rep[d >> 2], nb[d], 0, 0, 0, false) >> 24;
-            if (!lds_pair_add(s_pkey, s_pcnt, k, 1u)) {
-              bnd_spill(b, f, k, 1u);
-              s_spill = 1;
-            }
-          }
-        }
+    const uint64_t prev = wave_shr1_u64(kp);
+    const bool same = got && lane > 0 && prev == kp;
+    const uint64_t same_mask = __ballot(same);
+    const bool head = got && !same;
+    const uint32_t len = head ? run_len(same_mask, lane) : 1u;
+    const uint32_t incl_end = (uint32_t)__shfl((int)incl, (int)(lane + len - 1));
+    uint32_t slot = kNoPairSlot;
+    if (head) {
+      const uint32_t tot = incl_end - incl + cnt;
+      slot = lds_pair_add(s_pkey, s_pcnt, kp, tot);
+      if (slot == kNoPairSlot) {  // LDS table full
+        bnd_spill(b, f, kp, tot);
+        s_spill = 1;
       }
     }
-    // wave-aggregated append of the points into the LDS staging buffer
+    // the run's lanes take the slot its head counted into (lanes without points read
+    // the head below them, or themselves: any lane in range)
+    const uint64_t hb = __ballot(head) << (63 - lane);  // bit 63: this lane, below it the lanes below
+    slot = (uint32_t)__shfl((int)slot, hb ? (int)lane - __builtin_clzll(hb) : (int)lane);
+    // wave-aggregated append of the points into the LDS staging buffer: the slot, the
+    // row and the column once per step, per point b2w and the direction
     uint32_t wbase = 0;
     if (lane == 0 && wtot) wbase = atomicAdd(&s_npts, wtot);
     wbase = __shfl(wbase, 0);
-    uint32_t pos = wbase + below;
-    if (wbase + wtot <= (uint32_t)kBndStage) {  // (uniform) the usual step: every point staged
+    const uint32_t pos0 = wbase + below;
+    const bool fits = wbase + wtot <= (uint32_t)kBndStage;  // (uniform; a tile with a step that does not is crowded)
+    const uint32_t wxy = narrow_xy(xa, y);  // (the second pixel: + 1 << 13; columns of points are < 1023)
+    if (fits) {
+      uint32_t pos = pos0;
+      const uint32_t w0 = (slot << 23) | wxy;
 #pragma unroll
       for (int d = 0; d < 8; d++)
-        if ((hm >> d) & 1) s_pts[pos++] = make_qbp(rep[d >> 2], nb[d], xa + (d >> 2), y, d & 3, b2w[d >> 2]);
-    } else {
+        if ((hm >> d) & 1) s_pts[pos++] = (w0 + ((uint32_t)(d >> 2) << 13)) | (b2w[d >> 2] ? 4u : 0u) | (uint32_t)(d & 3);
+    }
+    // the lane's points in other pairs: counted one by one, their words restaged with
+    // the slot of their own insert
+    if (__ballot(xm != 0)) {
 #pragma unroll
-      for (int d = 0; d < 8; d++)
-        if ((hm >> d) & 1) {
-          const uint64_t k = make_qbp(rep[d >> 2], nb[d], xa + (d >> 2), y, d & 3, b2w[d >> 2]);
-          if (pos < (uint32_t)kBndStage) s_pts[pos] = k;
-          else if (pos < (uint32_t)g.bnd_region) pts_out[pos] = k;
-          else atomicOr(b.status + f, kStatusPointsOverflow);
-          pos++;
+      for (int d = 0; d < 8; d++) {
+        if ((xm >> d) & 1) {
+          // (labels read again: rare, and the ten of them need not stay live until here)
+          int e0 = (y - ty0) * kTC + cx + 1 + (d >> 2);
+          asm volatile("" : "+v"(e0));  // (a fresh read: not the step's earlier value kept live)
+          const int en = e0 + ((d & 3) == 0 ? 1 : (d & 3) == 1 ? kTC + 1 : (d & 3) == 2 ? kTC : kTC - 1);
+          const uint64_t k = make_qbp(s_tlab[e0], s_tlab[en], 0, 0, 0, false) >> 24;
+          const uint32_t sx = lds_pair_add(s_pkey, s_pcnt, k, 1u);
+          if (sx == kNoPairSlot) {
+            bnd_spill(b, f, k, 1u);
+            s_spill = 1;
+          } else if (fits) {
+            s_pts[pos0 + (uint32_t)__builtin_popcount(hm & ((1u << d) - 1u))] =
+                (((sx << 23) | wxy) + ((uint32_t)(d >> 2) << 13)) | (b2w[d >> 2] ? 4u : 0u) | (uint32_t)(d & 3);
+          }
         }
+      }
     }
   }
   __syncthreads();
@@ -1807,8 +1820,40 @@ __global__ __launch_bounds__(256) AT_BND_ATTR void k_boundary(DevBufs b, Geom g)
   const uint32_t total = s_npts;
   // narrow tile: every point staged and every pair in the LDS table -> 4-B points
   // carrying their entry index (half the bytes for k_group, which then needs no
-  // key lookup); otherwise the 8-B keys
+  // key lookup); otherwise (crowded) the 8-B keys
   const bool narrow = total <= (uint32_t)kBndStage && !s_spill;
+  if (!narrow) {
+    // crowded tile: the rows once more, the full keys straight to the tile's region
+    // (the histogram is complete; only the points' positions are taken again, from
+    // s_nent, which the entry compaction below starts from zero)
+    // (the lane's coordinates derived again from the thread index: kept live from the
+    // first pass they would cost it two registers, and with them an allocation step)
+    uint32_t wl = threadIdx.x, wt = threadIdx.y;
+    asm volatile("" : "+v"(wl), "+v"(wt));
+    const int wcx = 2 * (int)(wl & 31), wxa = 1 + bi.x * 64 + wcx;
+    for (int r = 0; r < kBndRows / 2; r++) {
+      uint32_t hm, nb[8], rep[2];
+      bool b2w[2];
+      const int y = step_points(r, (int)wt, wl, wcx, wxa, hm, nb, rep, b2w);
+      const uint32_t npts = (uint32_t)__builtin_popcount(hm);
+      const uint32_t sc = wave_incl_scan(npts, AddOp(), 0u);
+      const uint32_t wtot = wave_read(sc, 63);
+      uint32_t wbase = 0;
+      if (wl == 0 && wtot) wbase = atomicAdd(&s_nent, wtot);
+      wbase = __shfl(wbase, 0);
+      uint32_t pos = wbase + sc - npts;
+#pragma unroll
+      for (int d = 0; d < 8; d++)
+        if ((hm >> d) & 1) {
+          if (pos < (uint32_t)g.bnd_region) pts_out[pos] = make_qbp(rep[d >> 2], nb[d], wxa + (d >> 2), y, d & 3, b2w[d >> 2]);
+          else atomicOr(b.status + f, kStatusPointsOverflow);
+          pos++;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) s_nent = 0;
+    __syncthreads();
+  }
   uint64_t* ekey = b.pent_key + tb * kLdsPairSlots;
   uint32_t* ecnt = b.pent_cnt + tb * kLdsPairSlots;
   uint32_t* s_ent = s_tlab;  // slot -> entry index (the label table is dead)
@@ -1825,12 +1870,9 @@ __global__ __launch_bounds__(256) AT_BND_ATTR void k_boundary(DevBufs b, Geom g)
     __syncthreads();
     uint32_t* out = reinterpret_cast<uint32_t*>(pts_out);
     for (uint32_t i = tid; i < total; i += 256) {
-      const uint64_t k = s_pts[i];
-      out[i] = narrow_point(s_ent[lds_pair_slot(s_pkey, k >> 24)], k);
+      const uint32_t w = s_pts[i];
+      out[i] = (s_ent[w >> 23] << 23) | (w & 0x7fffffu);
     }
-  } else {
-    const uint32_t staged = total < (uint32_t)kBndStage ? total : (uint32_t)kBndStage;
-    for (uint32_t i = tid; i < staged; i += 256) pts_out[i] = s_pts[i];
   }
   __syncthreads();
   if (tid == 0) {
@@ -2212,9 +2254,12 @@ __global__ __launch_bounds__(1024) void k_pairs(DevBufs b, Geom g, int probe) {
 // bounds -- P4's size filter: nothing reads their segments); the tile's points
 // take consecutive slots of their entry's range (LDS cursor).  The tile's
 // counters, its entries and its first 512 points are loaded in ONE round trip
-// (speculatively: reads past the counts stay inside the tile's regions).  Points
-// of later entries (crowded tiles) and of pairs missing from the tile's entries
-// (LDS table overflow in k_boundary) reserve one slot each.
+// (speculatively: reads past the counts stay inside the tile's regions).  A
+// narrow tile (up to kBndStage = 2048 words: every tile of the camera stream, an
+// eighth of which hold more than 1024) takes the direct path below; a crowded one
+// (more points, or an LDS table overflow in k_boundary: dense synthetic patterns)
+// looks its 8-B keys up in an LDS table of the tile's entries.  Points of entries
+// past kGrpEnt and of pairs missing from the tile's entries reserve one slot each.
 // loaded up front, before the tile's counts are known: the first 256 8-B keys or 512
 // narrow words and 32 entries (typical tiles: ~700 narrow points, ~10 entries), so the
 // speculation reads nothing past the counts of most tiles; the rest follows once they
