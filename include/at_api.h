@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define AT_ABI_VERSION 7
+#define AT_ABI_VERSION 8
 
 enum {
   AT_OK = 0,
@@ -339,6 +339,45 @@ int at_draw_outlines_device(at_detector *d, const at_detection *dets, int n, uin
  * batch was host BGR8 frames or a colour-on MJPG batch (then the decoded image is what
  * is drawn on).  The staged copy is consumed (overwritten). */
 int at_annotate_staged(at_detector *d, int frame, const at_detection *dets, int n, uint8_t *bgr_out);
+
+/* The annotated image as a finished JPEG, encoded on the GPU: what the node's consumers
+ * read is the compressed topic (image_transport, the viewer's cv::imencode), so the image
+ * need not cross the link at 3 B per pixel to be encoded on a host core.
+ *
+ * The stream: baseline SOF0, 8 bit, YCbCr, one interleaved scan; sampling AT_JPEG_420 (what
+ * cv::imencode writes), AT_JPEG_422 or AT_JPEG_444; libjpeg's quality rule, quality 1..100
+ * (OpenCV's default is 95); the Annex K Huffman tables; one restart interval per MCU row
+ * (DRI = MCUs per row, RSTm between rows).  Header: SOI, a JFIF APP0, DQT, DQT, SOF0, four
+ * DHT, DRI, SOS.  Every non-APPn segment and the entropy-coded data equal byte for byte
+ * what libjpeg(-turbo) writes for the same image with its integer "slow" DCT and
+ * restart_in_rows = 1 (Pillow: save(..., restart_marker_rows=1)).
+ *
+ * at_encode_jpeg_device encodes a device-resident BGR8 image of the detector's geometry
+ * (width x height x 3, row-major, 8-byte aligned) on the detector's stream into host memory
+ * (the counterpart of at_draw_outlines_device); it returns when the bytes are in `out`.
+ * at_annotate_jpeg is at_annotate_staged with that encode in place of the raw copy: same
+ * gating (AT_E_INVALID unless the last batch was host BGR8 frames or a colour-on MJPG batch
+ * and `frame` one of its frames), the staged image is consumed, and only the stream's bytes
+ * cross the link.  *len receives the stream's size.  If it exceeds cap the result is
+ * AT_E_CAPACITY, *len is the size needed and nothing is written to `out`;
+ * at_jpeg_max_bytes(width, height, sampling) is a capacity no image can exceed (0 for a
+ * geometry the encoder does not take: multiples of 8 up to 65528).  quality outside 1..100
+ * or an unknown sampling: AT_E_INVALID.  The device buffers are allocated on the first call
+ * at the worst case of the geometry and kept.  `out` page-locked (at_host_alloc) is copied
+ * into by DMA.
+ * at_jpeg_stats, the last encode: [0] bytes of the stream, [1] the time of the encode
+ * kernels in nanoseconds (HIP events; measured while at_set_profiling is on, 0 otherwise).
+ * at_jpeg_encode_host is the same encoder on the host (no device needed; any width and
+ * height that are multiples of 8): the CPU reference, sharing the kernels' arithmetic. */
+enum { AT_JPEG_420 = 0, AT_JPEG_422 = 1, AT_JPEG_444 = 2 };
+int at_encode_jpeg_device(at_detector *d, const uint8_t *bgr, int quality, int sampling, uint8_t *out, size_t cap,
+                          size_t *len);
+int at_annotate_jpeg(at_detector *d, int frame, const at_detection *dets, int n, int quality, int sampling,
+                     uint8_t *out, size_t cap, size_t *len);
+size_t at_jpeg_max_bytes(int width, int height, int sampling);
+int at_jpeg_stats(at_detector *d, uint64_t *out, int cap);
+int at_jpeg_encode_host(const uint8_t *bgr, int width, int height, int quality, int sampling, uint8_t *out,
+                        size_t cap, size_t *len);
 
 /* Page-locked host memory (hipHostMalloc) for buffers the detector copies into on
  * its stream by DMA, e.g. at_annotate_staged's bgr_out: a pageable destination

@@ -8,12 +8,14 @@
 // (apriltags_cuda_detector.cu:382-557).  Publishers print one JSON line per
 // frame; --proto-out / --image-out write the ApriltagListProto bytes and the
 // outlined bgr8 image of the last frame (bgr8 input, or MJPG with --mjpg-color: the
-// frame's colour is then decoded on the GPU too).
+// frame's colour is then decoded on the GPU too).  --jpeg-out DIR: the outlined image is
+// JPEG-encoded on the GPU (DetectorCore::set_image_jpeg, --jpeg-quality Q, default 95) and
+// every frame's file written to DIR/frame_NNNNNN.jpg.
 //
 // usage: at_mock_node --camera-serial S --format bgr8|yuyv|gray|mjpg --frames F [--count N]
 //        [--vision-config-dir D] [--pin-to-core C --priority P]
 //        [--measurement-csv PATH] [--proto-out P] [--image-out I] [--device K] [--time N]
-//        [--mjpg-color]
+//        [--mjpg-color] [--jpeg-out DIR] [--jpeg-quality Q]
 //   As the reference node (apriltags_cuda_detector.cu:137-193): the frame size, the
 //   intrinsics and the extrinsics come from the camera serial's records in the
 //   vision_config_data share directory, found through $AMENT_PREFIX_PATH
@@ -32,6 +34,8 @@
 #include <fstream>
 #include <string>
 #include <vector>
+
+#include <sys/stat.h>
 
 #include "at_node.h"
 
@@ -82,8 +86,9 @@ std::vector<Span> split_mjpg(const std::vector<uint8_t>& d) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  int W = 0, H = 0, count = -1, device = 0, pin = -1, priority = 80, time_n = 0;
+  int W = 0, H = 0, count = -1, device = 0, pin = -1, priority = 80, time_n = 0, jpeg_quality = 95;
   std::string fmt_s = "yuyv", frames_path, calib_dir, serial = "N/A", sys_cfg, csv, proto_out, image_out, share_dir;
+  std::string jpeg_out;
   bool mjpg_color = false;
   for (int i = 1; i < argc; i += 2) {
     const std::string k = argv[i];
@@ -110,6 +115,8 @@ int main(int argc, char** argv) {
     else if (k == "--pin-to-core") pin = std::atoi(v.c_str());
     else if (k == "--priority") priority = std::atoi(v.c_str());
     else if (k == "--time") time_n = std::atoi(v.c_str());
+    else if (k == "--jpeg-out") jpeg_out = v;
+    else if (k == "--jpeg-quality") jpeg_quality = std::atoi(v.c_str());
     else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
   }
   at_node::Params prm;
@@ -177,6 +184,10 @@ int main(int argc, char** argv) {
     core.publish_camera = on_camera;
     core.ctx = &sink;
     if (mjpg && mjpg_color) core.set_mjpg_color(true);
+    if (!jpeg_out.empty()) {
+      core.set_image_jpeg(jpeg_quality);
+      ::mkdir(jpeg_out.c_str(), 0777);  // (exists already: fine)
+    }
     at_node::FrameOutputs out;
     at_node::ImageBuffer image;
     auto run = [&](int f, double stamp) {
@@ -248,7 +259,17 @@ int main(int argc, char** argv) {
         std::ofstream po(proto_out, std::ios::binary);
         po.write(out.proto.data(), (std::streamsize)out.proto.size());
       }
-      if (f == count - 1 && !image_out.empty() && !image.empty()) {
+      if (!jpeg_out.empty() && !image.empty()) {
+        char name[32];
+        std::snprintf(name, sizeof(name), "/frame_%06d.jpg", f);
+        std::ofstream jo(jpeg_out + name, std::ios::binary);
+        jo.write((const char*)image.data(), (std::streamsize)image.size());
+        if (!jo) {
+          std::fprintf(stderr, "cannot write %s%s\n", jpeg_out.c_str(), name);
+          return 1;
+        }
+      }
+      if (f == count - 1 && !image_out.empty() && !image.empty() && jpeg_out.empty()) {
         std::ofstream io(image_out, std::ios::binary);
         io.write((const char*)image.data(), (std::streamsize)image.size());
       }

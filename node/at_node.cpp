@@ -507,6 +507,16 @@ void DetectorCore::set_mjpg_color(bool on) {
   mjpg_color_ = on;
 }
 
+void DetectorCore::set_image_jpeg(int quality) {
+  if (quality < 0 || quality > 100) throw std::runtime_error("set_image_jpeg: quality 1..100 (0: off)");
+  if (quality && jpeg_buf_.empty()) {
+    const size_t most = at_jpeg_max_bytes(width_, height_, AT_JPEG_420);
+    if (!most) throw std::runtime_error("set_image_jpeg: no JPEG of this frame size");
+    jpeg_buf_.resize(most);
+  }
+  image_jpeg_ = quality;
+}
+
 // fmt < 0: `frame` is one MJPG frame of `len` bytes (at_detect_mjpg); the tail is the same
 int DetectorCore::run(const uint8_t* frame, size_t len, int fmt, double stamp_s, double receive_s, FrameOutputs* out,
                       ImageBuffer* annotate) {
@@ -541,9 +551,18 @@ int DetectorCore::run(const uint8_t* frame, size_t len, int fmt, double stamp_s,
     // draw_detection_outlines (:411) on the GPU, on the copy of the frame at_detect
     // staged in HBM: no host copy of the frame, no host drawing (an MJPG frame with
     // colour on: on the image decoded there)
-    annotate->resize((size_t)width_ * height_ * 3);
-    const int arc = at_annotate_staged(det_, 0, out->detections.data(), n, annotate->data());
-    if (arc != AT_OK) return arc;
+    if (image_jpeg_) {
+      // ... and encoded there: only the JPEG's bytes are copied out
+      size_t len = 0;
+      const int arc = at_annotate_jpeg(det_, 0, out->detections.data(), n, image_jpeg_, AT_JPEG_420, jpeg_buf_.data(),
+                                       jpeg_buf_.size(), &len);
+      if (arc != AT_OK) return arc;
+      annotate->assign(jpeg_buf_.begin(), jpeg_buf_.begin() + (ptrdiff_t)len);
+    } else {
+      annotate->resize((size_t)width_ * height_ * 3);
+      const int arc = at_annotate_staged(det_, 0, out->detections.data(), n, annotate->data());
+      if (arc != AT_OK) return arc;
+    }
   }
   const auto nt0 = clk::now();
   if (send_networktables) send_networktables(ctx, out->networktables_pose_data, out->proto);

@@ -240,6 +240,15 @@ class DetectorCore {
   int process_compressed(const uint8_t* data, size_t len, double stamp_s, double receive_s, FrameOutputs* out,
                          ImageBuffer* annotate = nullptr);
   void set_mjpg_color(bool on);
+  // set_image_jpeg(quality), 1..100 (0: off, the default): the annotated image is also
+  // JPEG-encoded on the GPU (at_annotate_jpeg, 4:2:0 as cv::imencode writes) and only the
+  // compressed bytes cross the link.  `annotate` then receives the JPEG file instead of the
+  // bgr8 image, and so do the publisher queue and publish_image: the transport publishes
+  // it as a CompressedImage on compressed_image_topic(), the topic the bag recording and
+  // the viewer read, and nothing on the raw one.
+  void set_image_jpeg(int quality);
+  int image_jpeg() const { return image_jpeg_; }
+  std::string compressed_image_topic() const { return params_.publish_images_to_topic + "/compressed"; }
 
   const Params& params() const { return params_; }
   int width() const { return width_; }
@@ -267,8 +276,10 @@ class DetectorCore {
   int width_, height_;
   Params params_;
   bool mjpg_color_ = false;
+  int image_jpeg_ = 0;
+  ImageBuffer jpeg_buf_;  // page-locked, at_jpeg_max_bytes: allocated by set_image_jpeg, reused
   struct StampedImage {
-    std::vector<uint8_t> bgr;
+    std::vector<uint8_t> bgr;  // the payload: bgr8, or the JPEG file with set_image_jpeg
     double stamp_s = 0;
   };
   std::unique_ptr<PublisherQueue<StampedImage>> image_queue_;

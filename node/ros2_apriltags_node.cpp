@@ -7,7 +7,10 @@
 // pin_to_core, priority, measurement_mode, timing_csv_path), subscription QoS (depth 1,
 // best effort, volatile, 50 ms deadline), TagDetectionArray publishers on <pose> (robot
 // frame) and <pose>_camera, the outlined bgr8 image through a drop-oldest publisher
-// queue.  Set-up as the reference's (apriltags_cuda_detector.cu:137-193, 601-605): frame
+// queue -- or, with the parameter image_jpeg set to a quality 1..100 (default 0: off), the
+// same image JPEG-encoded on the GPU as a sensor_msgs/CompressedImage on
+// <publish_images_to_topic>/compressed (the topic the bag recording and the viewer read)
+// and nothing on the raw topic.  Set-up as the reference's (apriltags_cuda_detector.cu:137-193, 601-605): frame
 // W x H, intrinsics and extrinsics from the camera serial's records in
 // vision_config_data's share directory (ament_index), then CPU pinning + SCHED_FIFO.
 // The launch file (launch_vision.py:283-305) passes nothing else.
@@ -23,6 +26,7 @@
 #include "apriltags_cuda/msg/tag_detection_array.hpp"
 #include "at_node.h"
 #include "rclcpp/rclcpp.hpp"
+#include "sensor_msgs/msg/compressed_image.hpp"
 #include "sensor_msgs/msg/image.hpp"
 
 class ApriltagsAmdNode : public rclcpp::Node {
@@ -37,6 +41,7 @@ class ApriltagsAmdNode : public rclcpp::Node {
     p.priority = declare_parameter<int>("priority", p.priority);
     p.measurement_mode = declare_parameter<bool>("measurement_mode", p.measurement_mode);
     p.timing_csv_path = declare_parameter<std::string>("timing_csv_path", p.timing_csv_path);
+    const int image_jpeg = declare_parameter<int>("image_jpeg", 0);
     // optional override of the share directory (not passed by the launch file)
     std::string share_dir = declare_parameter<std::string>("vision_config_dir", "");
     if (share_dir.empty()) {
@@ -65,8 +70,18 @@ class ApriltagsAmdNode : public rclcpp::Node {
     core_->publish_camera = [](void* c, const std::vector<at_node::TagDetectionMsg>& v) {
       static_cast<ApriltagsAmdNode*>(c)->camera_pose_pub_->publish(to_msg(v));
     };
+    if (image_jpeg) core_->set_image_jpeg(image_jpeg);
     core_->publish_image = [](void* c, const std::vector<uint8_t>& bgr, double stamp_s) {
       auto* self = static_cast<ApriltagsAmdNode*>(c);  // publisher-queue thread
+      if (self->core_->image_jpeg()) {  // the payload is the JPEG file
+        auto jmsg = std::make_unique<sensor_msgs::msg::CompressedImage>();
+        jmsg->header.stamp = rclcpp::Time(static_cast<int64_t>(stamp_s * 1e9));
+        jmsg->header.frame_id = "apriltag_detections";
+        jmsg->format = "jpeg";
+        jmsg->data = bgr;
+        self->compressed_pub_->publish(std::move(jmsg));
+        return;
+      }
       auto msg = std::make_unique<sensor_msgs::msg::Image>();
       msg->header.stamp = rclcpp::Time(static_cast<int64_t>(stamp_s * 1e9));  // image_capture_time (:516)
       msg->header.frame_id = "apriltag_detections";
@@ -84,7 +99,10 @@ class ApriltagsAmdNode : public rclcpp::Node {
         p.topic_name, qos, [this](sensor_msgs::msg::Image::SharedPtr m) { on_image(m); });
     pose_pub_ = create_publisher<apriltags_cuda::msg::TagDetectionArray>(p.publish_pose_to_topic, 10);
     camera_pose_pub_ = create_publisher<apriltags_cuda::msg::TagDetectionArray>(core_->camera_pose_topic(), 10);
-    image_pub_ = create_publisher<sensor_msgs::msg::Image>(p.publish_images_to_topic, 10);
+    if (image_jpeg)
+      compressed_pub_ = create_publisher<sensor_msgs::msg::CompressedImage>(core_->compressed_image_topic(), 10);
+    else
+      image_pub_ = create_publisher<sensor_msgs::msg::Image>(p.publish_images_to_topic, 10);
     std::string sched_log;  // applyCpuPinningAndScheduling (:601-605)
     at_node::apply_cpu_pinning_and_scheduling(p.pin_to_core, p.priority, &sched_log);
     RCLCPP_INFO(get_logger(), "%s", sched_log.c_str());
@@ -144,6 +162,7 @@ class ApriltagsAmdNode : public rclcpp::Node {
   at_node::ImageBuffer image_;  // page-locked: the annotated image arrives by DMA
   rclcpp::Publisher<apriltags_cuda::msg::TagDetectionArray>::SharedPtr pose_pub_, camera_pose_pub_;
   rclcpp::Publisher<sensor_msgs::msg::Image>::SharedPtr image_pub_;
+  rclcpp::Publisher<sensor_msgs::msg::CompressedImage>::SharedPtr compressed_pub_;
   // after the publishers: destroyed first (members go in reverse order), so the
   // publisher-queue thread never outlives image_pub_
   std::unique_ptr<at_node::DetectorCore> core_;

@@ -34,6 +34,8 @@ hipError_t launch_mjpg_idct(const uint8_t* coef, size_t slot, uint8_t* out, size
 hipError_t launch_mjpg_color(const uint8_t* coef, size_t slot, const uint8_t* gray, uint8_t* planes,
                              size_t plane_stride, uint8_t* bgr, size_t img_stride, int W, int H, int nframes,
                              hipStream_t st);
+hipError_t launch_jpg_encode(const uint8_t* bgr, int W, int H, int quality, int sampling, const JpgBufs& b,
+                             hipStream_t st);
 hipError_t prepare_kernels(const Geom& g);
 hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, int B, int fmt, int nblobwg,
                            hipStream_t st, hipEvent_t* ev, hipStream_t st2, hipEvent_t fork, hipEvent_t join,
@@ -119,6 +121,8 @@ using namespace at;
 
 static_assert(kMjpgInvalid == AT_E_INVALID && kMjpgUnsupported == AT_E_UNSUPPORTED && kMjpgOk == AT_OK,
               "at_mjpg.h carries the ABI's codes");
+static_assert(kJpg420 == AT_JPEG_420 && kJpg422 == AT_JPEG_422 && kJpg444 == AT_JPEG_444 && AT_E_CAPACITY == -3,
+              "at_mjpg.h carries the ABI's sampling codes");
 
 // control block layout (u32 words, zeroed every batch): per-frame arrays of B
 // words, then scalars
@@ -215,6 +219,16 @@ struct at_detector {
   uint8_t* d_mj_planes;     // [B][2][mj_plane]
   size_t mj_plane;
   uint8_t* d_mj_bgr;        // [B][in_stride]
+  // JPEG output (at_encode_jpeg_device), allocated on the first call at the worst case of
+  // this geometry (4:4:4, every block at its longest, every byte stuffed) and kept
+  at::JpgBufs jpg;
+  size_t jpg_out_cap;       // bytes of jpg.out
+  uint32_t* h_jpg_total;    // mapped, page-locked: where k_jpg_pack leaves the length
+  uint8_t jpg_hdr[at::kJpgHeaderMax];  // SOI .. SOS of the last (quality, sampling)
+  size_t jpg_hdr_len;
+  int jpg_hdr_q, jpg_hdr_s;
+  uint64_t jpg_stats[2];    // last encode: bytes out, the encode kernels' ns (while profiling)
+  hipEvent_t ev_jpg[2];     // around them (created on first use)
 };
 
 // Experiment and diagnostic knobs (stage cut-offs, grid / tile overrides, phase
@@ -319,6 +333,9 @@ void at_destroy(at_detector* d) {
     if (p) (void)hipHostFree(p);
   for (hipEvent_t e : d->ev_mj)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : d->ev_jpg)
+    if (e) (void)hipEventDestroy(e);
+  if (d->h_jpg_total) (void)hipHostFree(d->h_jpg_total);
   if (d->ev_done) (void)hipEventDestroy(d->ev_done);
   if (d->ev_ext) (void)hipEventDestroy(d->ev_ext);
   for (int i = 0; i <= kNumStages; i++)
@@ -1359,6 +1376,125 @@ int at_annotate_staged(at_detector* d, int frame, const at_detection* dets, int 
   HIPCHK(hipMemcpyAsync(bgr_out, img, (size_t)d->g.W * d->g.H * 3, hipMemcpyDeviceToHost, d->st));
   HIPCHK(hipStreamSynchronize(d->st));
   return AT_OK;
+}
+
+// ---- JPEG output ----------------------------------------------------------------
+// The annotated image leaves the GPU as a finished baseline JPEG (k_jpg_fdct, the four
+// entropy-coding launches, k_jpg_pack on the detector's stream, outside the captured graphs).  The header is written
+// by the host; k_jpg_pack leaves the length of what follows it in a mapped host word, the
+// host waits for the stream, checks the capacity and copies exactly those bytes.
+static int jpeg_prepare(at_detector* d) {
+  if (d->jpg.coef) return AT_OK;
+  size_t coef_b = 0, bits_w = 0, out_b = 0, rows = 0;
+  for (int s : {kJpg420, kJpg422, kJpg444}) {
+    JpgGeom g;
+    if (!jpg_geom(d->g.W, d->g.H, s, &g)) return AT_E_INVALID;  // wider or taller than a JPEG can be
+    const size_t nbr = (size_t)g.mcux * g.bpm;
+    coef_b = std::max(coef_b, nbr * g.mcuy * 128);
+    bits_w = std::max(bits_w, (nbr * (kJpgBlockBytes / 4) + 4) * g.mcuy);
+    out_b = std::max(out_b, jpg_max_bytes(d->g.W, d->g.H, s) - kJpgHeaderMax);
+    rows = std::max(rows, (size_t)g.mcuy);
+  }
+  uint32_t tab[kJpgTabWords];
+  jpg_huff_tables(tab);
+  void *coef = nullptr, *dtab = nullptr, *bits = nullptr, *rowv = nullptr, *out = nullptr, *blen = nullptr;
+  uint32_t* total = nullptr;
+  if (hipMalloc(&coef, coef_b) != hipSuccess || hipMalloc(&dtab, sizeof(tab)) != hipSuccess ||
+      hipMalloc(&bits, bits_w * 4) != hipSuccess || hipMalloc(&rowv, 2 * rows * 4) != hipSuccess ||
+      hipMalloc(&out, out_b) != hipSuccess || hipMalloc(&blen, coef_b / 128 * 4) != hipSuccess ||
+      hipHostMalloc((void**)&total, 64, hipHostMallocMapped) != hipSuccess) {
+    for (void* p : {coef, dtab, bits, rowv, out, blen})
+      if (p) (void)hipFree(p);
+    return AT_E_NOMEM;
+  }
+  for (void* p : {coef, dtab, bits, rowv, out, blen}) d->allocs.push_back(p);
+  d->h_jpg_total = total;
+  *total = 0;
+  HIPCHK(hipMemcpy(dtab, tab, sizeof(tab), hipMemcpyHostToDevice));
+  HIPCHK(hipHostGetDevicePointer((void**)&d->jpg.total, total, 0));
+  d->jpg.tab = (const uint32_t*)dtab;
+  d->jpg.bits = (uint32_t*)bits;
+  d->jpg.blen = (uint32_t*)blen;
+  d->jpg.row_raw = (uint32_t*)rowv;
+  d->jpg.row_len = (uint32_t*)rowv + rows;
+  d->jpg.out = (uint8_t*)out;
+  d->jpg_out_cap = out_b;
+  d->jpg.coef = (int16_t*)coef;
+  return AT_OK;
+}
+
+// `img` (device, the detector's geometry) encoded on the detector's stream behind what is
+// queued there; returns when the bytes are in `out`
+static int encode_jpeg(at_detector* d, const uint8_t* img, int quality, int sampling, uint8_t* out, size_t cap,
+                       size_t* len) {
+  JpgGeom g;
+  if (quality < 1 || quality > 100 || !jpg_geom(d->g.W, d->g.H, sampling, &g) || ((uintptr_t)img & 7))
+    return AT_E_INVALID;
+  const int prc = jpeg_prepare(d);
+  if (prc != AT_OK) return prc;
+  if (!d->jpg_hdr_len || d->jpg_hdr_q != quality || d->jpg_hdr_s != sampling) {
+    d->jpg_hdr_len = jpg_write_header(d->jpg_hdr, d->g.W, d->g.H, quality, sampling);
+    d->jpg_hdr_q = quality;
+    d->jpg_hdr_s = sampling;
+  }
+  d->jpg.row_words = (size_t)g.mcux * g.bpm * (kJpgBlockBytes / 4) + 4;
+  const bool timed = d->profiling != 0;
+  if (timed) {
+    for (hipEvent_t& e : d->ev_jpg)
+      if (!e) HIPCHK(hipEventCreateWithFlags(&e, kTimingEventFlags));
+    HIPCHK(hipEventRecord(d->ev_jpg[0], d->st));
+  }
+  HIPCHK(launch_jpg_encode(img, d->g.W, d->g.H, quality, sampling, d->jpg, d->st));
+  if (timed) HIPCHK(hipEventRecord(d->ev_jpg[1], d->st));
+  HIPCHK(hipStreamSynchronize(d->st));
+  const size_t body = *(volatile uint32_t*)d->h_jpg_total;
+  if (body > d->jpg_out_cap) return AT_E_HIP;  // (cannot happen: the buffers hold the worst case)
+  const size_t need = d->jpg_hdr_len + body;
+  *len = need;
+  d->jpg_stats[0] = need;
+  d->jpg_stats[1] = 0;
+  if (timed) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, d->ev_jpg[0], d->ev_jpg[1]));
+    d->jpg_stats[1] = (uint64_t)((double)ms * 1e6);
+  }
+  if (need > cap) return AT_E_CAPACITY;
+  memcpy(out, d->jpg_hdr, d->jpg_hdr_len);
+  // DMA straight into a page-locked `out` (at_host_alloc)
+  HIPCHK(hipMemcpyAsync(out + d->jpg_hdr_len, d->jpg.out, body, hipMemcpyDeviceToHost, d->st));
+  HIPCHK(hipStreamSynchronize(d->st));
+  return AT_OK;
+}
+
+int at_encode_jpeg_device(at_detector* d, const uint8_t* bgr, int quality, int sampling, uint8_t* out, size_t cap,
+                          size_t* len) {
+  if (len) *len = 0;
+  if (!d || !bgr || !out || !len) return AT_E_INVALID;
+  HIPCHK(hipSetDevice(d->device));
+  return encode_jpeg(d, bgr, quality, sampling, out, cap, len);
+}
+
+int at_annotate_jpeg(at_detector* d, int frame, const at_detection* dets, int n, int quality, int sampling,
+                     uint8_t* out, size_t cap, size_t* len) {
+  if (len) *len = 0;
+  if (!d || !out || !len || n < 0 || (n > 0 && !dets)) return AT_E_INVALID;
+  if (!d->last_staged || (d->last_fmt != AT_FMT_BGR8 && !d->last_mj_color) || frame < 0 || frame >= d->last_nframes)
+    return AT_E_INVALID;
+  JpgGeom g;
+  if (quality < 1 || quality > 100 || !jpg_geom(d->g.W, d->g.H, sampling, &g)) return AT_E_INVALID;
+  HIPCHK(hipSetDevice(d->device));
+  if (d->pending) HIPCHK(hipEventSynchronize(d->ev_done));
+  uint8_t* img = (d->last_mj_color ? d->d_mj_bgr : d->d_in) + (size_t)frame * d->in_stride;
+  const int rc = draw_outlines(d, dets, n, img);
+  if (rc != AT_OK) return rc;
+  return encode_jpeg(d, img, quality, sampling, out, cap, len);
+}
+
+int at_jpeg_stats(at_detector* d, uint64_t* out, int cap) {
+  if (!d || !out || cap < 1) return AT_E_INVALID;
+  const int n = std::min(cap, 2);
+  for (int i = 0; i < n; i++) out[i] = d->jpg_stats[i];
+  return n;
 }
 
 int at_host_alloc(size_t bytes, void** out) {

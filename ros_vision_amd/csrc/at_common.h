@@ -254,6 +254,20 @@ struct DrawPrim {
   uint8_t bgr[3];
 };
 
+// Buffers of the JPEG output (at_encode_jpeg_device), sized for 4:4:4 at the detector's
+// geometry; rows = MCU rows, each one restart interval.
+struct JpgBufs {
+  int16_t* coef;        // [blocks][64] quantised coefficients, zig-zag order, MCU scan order
+  const uint32_t* tab;  // the Annex K tables as code | length << 16 (jpg_huff_tables)
+  uint32_t* blen;       // [blocks] each block's bit length, then its bit offset in its row
+  uint32_t* bits;       // [rows][row_words] each row's unstuffed bit stream, padded to a byte
+  size_t row_words;     // >= 52 words per block of the longest row, + 4
+  uint32_t* row_raw;    // [rows] bytes of the row's stream in `bits`
+  uint32_t* row_len;    // [rows] ... after byte stuffing
+  uint8_t* out;         // the entropy-coded data with RSTm and EOI, what follows the header
+  uint32_t* total;      // bytes in `out` (mapped host memory)
+};
+
 // Device buffers; every per-frame array is [max_batch][per-frame size].
 struct DevBufs {
   const uint8_t* const* frames;   // device table of frame pointers

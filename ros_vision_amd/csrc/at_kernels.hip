@@ -5656,6 +5656,398 @@ hipError_t launch_mjpg_color(const uint8_t* coef, size_t slot, const uint8_t* gr
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// JPEG output: a device-resident BGR8 image (the annotated one) as a baseline JPEG,
+// byte for byte what libjpeg's integer "slow" path writes with one restart interval per
+// MCU row (at_mjpg.h has the shared arithmetic, at_jpeg_encode_host the sequential
+// reference).  Six launches on the detector's stream, none waiting for another
+// workgroup, every loop bounded by counts known at launch:
+//   k_jpg_fdct  colour conversion, chroma downsampling with libjpeg's edge rules, forward
+//               DCT, quantisation: every block's 64 coefficients as i16 in zig-zag order,
+//               blocks in MCU scan order, the dummy luma blocks of partial MCUs in place
+//   k_jpg_len   a lane per block, the whole picture at once: the block's bit length
+//   k_jpg_rows  one workgroup per MCU row (= restart interval): a scan turns the lengths
+//               into bit offsets; zeroes the row's bit buffer, pads its last byte
+//   k_jpg_bits  a lane per block again: writes the block's bits at its offset
+//   k_jpg_ff    one workgroup per MCU row: counts the row's FF bytes
+//   k_jpg_pack  one workgroup per MCU row: sums the stuffed lengths of the rows before it
+//               (launch order is the only ordering), then copies its row behind them with
+//               FF -> FF 00 and its RSTm (the last row: EOI and the total length)
+// Integers only.
+//
+// k_jpg_fdct: k_mjpg_idct's mapping mirrored.  256 threads take 32 consecutive blocks, 8
+// lanes per block, LDS int32 at word 72 * block + 8 * row + column:
+//   rows    lane j of a block loads row j's 8 pixels (24 bytes as three 8-byte loads; a
+//           subsampled chroma row 2 x 8 pixels of one or two picture rows), converts,
+//           downsamples, runs the 1-D pass in registers and writes its row (2 x 16 bytes)
+//   columns lane c reads column c (ds_read_b32 at 72 * block + 8 * r + c: the 32 lanes of a
+//           half wave cover 4 blocks x 8 columns = banks 8 * block + c, no conflict), runs
+//           the pass, quantises and writes the values back in place
+//   output  lane j gathers zig-zag positions 8j .. 8j+7 and stores them as one 16-byte word,
+//           consecutive lanes consecutive addresses
+// ---------------------------------------------------------------------------
+__constant__ uint8_t c_jpg_qbase[2][64] = {AT_JPG_QBASE_LUMA, AT_JPG_QBASE_CHROMA};
+
+// 8 BGR8 pixels (24 bytes, 8-byte aligned) as 6 dwords
+__device__ __forceinline__ void jpg_load8(const uint8_t* __restrict__ p, uint32_t (&w)[6]) {
+  const uint2* q = reinterpret_cast<const uint2*>(p);
+  const uint2 a = q[0], b = q[1], c = q[2];
+  w[0] = a.x; w[1] = a.y; w[2] = b.x; w[3] = b.y; w[4] = c.x; w[5] = c.y;
+}
+// component `comp` of pixel i (a constant after unrolling) of those
+__device__ __forceinline__ int32_t jpg_px(const uint32_t (&w)[6], int i, int comp) {
+  const int b = 3 * i, g = 3 * i + 1, r = 3 * i + 2;
+  return mjpg_ycc(comp, (int32_t)((w[r >> 2] >> (8 * (r & 3))) & 0xff), (int32_t)((w[g >> 2] >> (8 * (g & 3))) & 0xff),
+                  (int32_t)((w[b >> 2] >> (8 * (b & 3))) & 0xff));
+}
+
+__global__ __launch_bounds__(256) void k_jpg_fdct(const uint8_t* __restrict__ bgr, int16_t* __restrict__ coef, int W,
+                                                  int H, int sampling, int quality, uint32_t nblk) {
+  __shared__ __attribute__((aligned(16))) int32_t ws[kMjpgBlocksPerWg * kMjpgLdsStride];
+  __shared__ uint16_t qs[2][64];
+  JpgGeom g;
+  jpg_geom(W, H, sampling, &g);  // (checked by the host)
+  const int t = threadIdx.x;
+  if (t < 128) qs[t >> 6][t & 63] = (uint16_t)mjpg_quant_entry(c_jpg_qbase[t >> 6][t & 63], quality);
+  const int lb = t >> 3, j = t & 7;
+  const uint32_t blk = blockIdx.x * kMjpgBlocksPerWg + lb;
+  // (the surplus lanes of the last workgroup work on the last block and store nothing)
+  const uint32_t bs = min(blk, nblk - 1);
+  const uint32_t mcu = bs / (uint32_t)g.bpm;
+  const int k = (int)(bs - mcu * (uint32_t)g.bpm);
+  const int my = (int)(mcu / (uint32_t)g.mcux), mx = (int)(mcu - (uint32_t)my * (uint32_t)g.mcux);
+  const int nluma = g.hs * g.vs;
+  const size_t pitch = (size_t)W * 3;
+  int comp = 0;
+  bool dummy = false;
+  int32_t s[8];
+  if (k < nluma) {
+    // luma; a block beyond the picture repeats the DC of the block before it in the MCU: of
+    // its left neighbour, or (a whole dummy row) of the last block of the MCU's upper row,
+    // itself maybe such a copy -- so it transforms that real block and keeps the DC only
+    const int bx = mx * g.hs + (k & (g.hs - 1)), by = my * g.vs + (g.hs == 2 ? k >> 1 : 0);
+    dummy = bx >= g.bw || by >= g.bh;
+    const int sbx = min(by >= g.bh ? mx * g.hs + g.hs - 1 : bx, g.bw - 1), sby = min(by, g.bh - 1);
+    uint32_t w[6];
+    jpg_load8(bgr + (size_t)(sby * 8 + j) * pitch + (size_t)sbx * 24, w);
+#pragma unroll
+    for (int i = 0; i < 8; i++) s[i] = jpg_px(w, i, 0) - 128;
+  } else {
+    comp = k - nluma + 1;
+    // the chroma plane runs on below its real samples by repeating the last downsampled row
+    const int cy = min(my * 8 + j, g.ch - 1);
+    if (g.hs == 1) {
+      uint32_t w[6];
+      jpg_load8(bgr + (size_t)cy * pitch + (size_t)mx * 24, w);
+#pragma unroll
+      for (int i = 0; i < 8; i++) s[i] = jpg_px(w, i, comp) - 128;
+    } else {
+      // 16 pixels of one (4:2:2) or two (4:2:0) rows; where the picture ends after the
+      // first 8, the last input column is repeated
+      const bool wide = mx * 16 + 16 <= W;
+      int32_t c[2][16];
+#pragma unroll
+      for (int rr = 0; rr < 2; rr++) {
+        if (rr < g.vs) {
+          const uint8_t* row = bgr + (size_t)(cy * g.vs + rr) * pitch + (size_t)mx * 48;
+          uint32_t w[6];
+          jpg_load8(row, w);
+#pragma unroll
+          for (int i = 0; i < 8; i++) c[rr][i] = jpg_px(w, i, comp);
+          if (wide) {
+            jpg_load8(row + 24, w);
+#pragma unroll
+            for (int i = 0; i < 8; i++) c[rr][8 + i] = jpg_px(w, i, comp);
+          } else {
+#pragma unroll
+            for (int i = 0; i < 8; i++) c[rr][8 + i] = c[rr][7];
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < 16; i++) c[rr][i] = 0;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 8; i++)
+        s[i] = (g.vs == 2 ? mjpg_down_h2v2(c[0][2 * i], c[0][2 * i + 1], c[1][2 * i], c[1][2 * i + 1], i)
+                          : mjpg_down_h2v1(c[0][2 * i], c[0][2 * i + 1], i)) - 128;
+    }
+  }
+  mjpg_fdct_1d<0>(s);
+  {
+    int4* row = reinterpret_cast<int4*>(ws + lb * kMjpgLdsStride + 8 * j);
+    row[0] = make_int4(s[0], s[1], s[2], s[3]);
+    row[1] = make_int4(s[4], s[5], s[6], s[7]);
+  }
+  __syncthreads();
+  {
+    // column pass: lane j is column j of block lb
+    int32_t* col = ws + lb * kMjpgLdsStride + j;
+    const uint16_t* q = qs[comp ? 1 : 0] + j;
+    int32_t v[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) v[r] = col[8 * r];
+    mjpg_fdct_1d<1>(v);
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      const int32_t c = mjpg_quantise(v[r], (int32_t)q[8 * r]);
+      col[8 * r] = (dummy && (r | j)) ? 0 : c;
+    }
+  }
+  __syncthreads();
+  {
+    const int32_t* b = ws + lb * kMjpgLdsStride;
+    uint32_t u[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint32_t lo = (uint32_t)b[c_mjpg_zigzag[8 * j + 2 * i]] & 0xffffu;
+      const uint32_t hi = (uint32_t)b[c_mjpg_zigzag[8 * j + 2 * i + 1]] & 0xffffu;
+      u[i] = lo | (hi << 16);
+    }
+    if (blk < nblk) *reinterpret_cast<uint4*>(coef + (size_t)blk * 64 + 8 * j) = make_uint4(u[0], u[1], u[2], u[3]);
+  }
+}
+
+// One block's symbols in coding order: put(bits, length) for the DC difference and for every
+// run/size symbol with its magnitude bits (at most 26 bits a call), ZRL and EOB included.
+// zz: the block's 64 coefficients (16-byte aligned); dc / ac: the component's tables.
+template <typename Put>
+__device__ __forceinline__ void jpg_walk_block(const int16_t* __restrict__ zz, int32_t pred,
+                                               const uint32_t* dc, const uint32_t* ac, Put&& put) {
+  const uint4* p = reinterpret_cast<const uint4*>(zz);
+  int run = 0;
+  uint4 next = p[0];
+#pragma unroll 1
+  for (int i = 0; i < 8; i++) {
+    const uint4 v = next;
+    next = p[min(i + 1, 7)];  // in flight while these eight are coded
+    const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const int32_t c = (int32_t)(int16_t)((k & 1) ? (u[k >> 1] >> 16) : (u[k >> 1] & 0xffffu));
+      if (k == 0 && i == 0) {
+        const int32_t diff = c - pred;
+        const int n = mjpg_nbits(diff, 11);
+        const uint32_t e = dc[n];
+        put(((e & 0xffffu) << n) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << n) - 1u)), (int)(e >> 16) + n);
+        continue;
+      }
+      if (c == 0) {
+        run++;
+        continue;
+      }
+      for (; run > 15; run -= 16) put(ac[0xf0] & 0xffffu, (int)(ac[0xf0] >> 16));  // ZRL, at most 3
+      const int n = mjpg_nbits(c, 10);
+      const uint32_t e = ac[(run << 4) | n];
+      put(((e & 0xffffu) << n) | ((uint32_t)(c < 0 ? c - 1 : c) & ((1u << n) - 1u)), (int)(e >> 16) + n);
+      run = 0;
+    }
+  }
+  if (run) put(ac[0] & 0xffffu, (int)(ac[0] >> 16));  // EOB
+}
+
+// MSB-first bit writer of one block into the row's zeroed bit buffer, from bit `start`.  The
+// stream is kept as bytes in stream order, so a 32-bit group goes out byte-swapped.  A word
+// the block shares with a neighbour (its first, unless it starts on a word, and its last,
+// unless it ends on one) is combined by atomicOr; the words between are the block's alone
+// and stored plainly.
+struct JpgBitWriter {
+  uint32_t* buf;
+  uint32_t w;
+  uint64_t acc;
+  int n;
+  bool shared;
+  __device__ __forceinline__ JpgBitWriter(uint32_t* b, uint32_t start)
+      : buf(b), w(start >> 5), acc(0), n((int)(start & 31)), shared((start & 31) != 0) {}
+  __device__ __forceinline__ void put(uint32_t bits, int len) {  // len <= 26, n < 32: at most 57 bits held
+    acc = (acc << len) | bits;
+    n += len;
+    if (n >= 32) {
+      n -= 32;
+      const uint32_t word = __builtin_bswap32((uint32_t)(acc >> n));
+      acc &= (1ull << n) - 1ull;
+      if (shared)
+        atomicOr(buf + w, word);
+      else
+        buf[w] = word;
+      shared = false;
+      w++;
+    }
+  }
+  __device__ __forceinline__ void finish() {
+    if (n) atomicOr(buf + w, __builtin_bswap32((uint32_t)(acc << (32 - n))));
+  }
+};
+
+__device__ __forceinline__ uint32_t jpg_count_ff(uint32_t w) {
+  return ((w & 0xffu) == 0xffu) + ((w & 0xff00u) == 0xff00u) + ((w & 0xff0000u) == 0xff0000u) + (w >= 0xff000000u);
+}
+
+// The entropy coding of the coefficient buffer, as four launches.  nbr: blocks of one MCU row
+// (MCUs per row * bpm), nluma = hs * vs luma blocks lead each MCU, nblk = nbr * rows.
+// The row's bit buffer holds 52 words per block and 4 more (JpgBufs::row_words): a block
+// takes at most 22 + 63 * 26 = 1660 bits, so bit offsets stay below 1664 * nbr and the word
+// after the last one used, which k_jpg_rows' zeroing reaches, is inside the row's share.
+//
+// What a lane needs to code block `blk` of the buffer: its coefficients, the DC of the block
+// before of the same component inside the restart interval (a luma block's is its neighbour
+// or the last luma block of the MCU before, behind that one's Cb and Cr), its tables.
+struct JpgBlockRef {
+  const int16_t* zz;
+  int32_t pred;
+  const uint32_t *dc, *ac;
+};
+__device__ __forceinline__ JpgBlockRef jpg_block_ref(const JpgBufs& b, const uint32_t* s_tab, uint32_t blk, int nbr,
+                                                     int bpm, int nluma) {
+  const uint32_t r = blk / (uint32_t)nbr;
+  const int i = (int)(blk - r * (uint32_t)nbr);  // block of its row
+  const int k = i % bpm;
+  const bool chroma = k >= nluma;
+  const int prev = chroma ? i - bpm : (k ? i - 1 : i - 3);
+  JpgBlockRef ref;
+  ref.zz = b.coef + (size_t)blk * 64;
+  ref.pred = prev >= 0 ? ref.zz[(ptrdiff_t)(prev - i) * 64] : 0;
+  ref.dc = s_tab + (chroma ? kJpgDcTab : 0);
+  ref.ac = s_tab + 2 * kJpgDcTab + (chroma ? kJpgAcTab : 0);
+  return ref;
+}
+
+// every block's bit length: a lane per block, all blocks of the picture at once
+__global__ __launch_bounds__(256) void k_jpg_len(JpgBufs b, uint32_t nblk, int nbr, int bpm, int nluma) {
+  __shared__ uint32_t s_tab[kJpgTabWords];
+  for (int i = threadIdx.x; i < kJpgTabWords; i += 256) s_tab[i] = b.tab[i];
+  __syncthreads();
+  const uint32_t blk = blockIdx.x * 256 + threadIdx.x;
+  if (blk >= nblk) return;
+  const JpgBlockRef ref = jpg_block_ref(b, s_tab, blk, nbr, bpm, nluma);
+  uint32_t len = 0;
+  jpg_walk_block(ref.zz, ref.pred, ref.dc, ref.ac, [&](uint32_t, int l) { len += (uint32_t)l; });
+  b.blen[blk] = len;
+}
+
+// one workgroup per MCU row (= restart interval): the lengths scanned into every block's bit
+// offset in the row (256 lanes, looping with a carry when the row has more blocks), the
+// words the row will use zeroed, the last byte padded with 1-bits
+constexpr int kJpgRowThreads = 256;
+__global__ __launch_bounds__(kJpgRowThreads) void k_jpg_rows(JpgBufs b, int nbr) {
+  __shared__ uint32_t s_tmp[kJpgRowThreads / 64];
+  const int t = threadIdx.x;
+  const uint32_t r = blockIdx.x;
+  uint32_t* rb = b.bits + (size_t)r * b.row_words;
+  uint32_t* len = b.blen + (size_t)r * (size_t)nbr;  // length in, offset out
+  uint32_t base = 0;
+  for (int c0 = 0; c0 < nbr; c0 += kJpgRowThreads) {
+    const int i = c0 + t;
+    const uint32_t l = i < nbr ? len[i] : 0u;
+    uint32_t total;
+    const uint32_t incl = block_incl_scan(l, s_tmp, &total, kJpgRowThreads / 64);
+    if (i < nbr) len[i] = base + incl - l;
+    base += total;
+  }
+  // zero as far as the row will be used and one word more; the word the stream ends in
+  // starts out as the 1-bits that pad its last byte
+  const uint32_t wend = (base + 31) / 32 + 1, pad = (8 - (base & 7)) & 7;
+  const uint32_t padword = __builtin_bswap32(pad ? ((1u << pad) - 1u) << (32 - (base & 31) - pad) : 0u);
+  for (uint32_t w = t; w < wend; w += kJpgRowThreads) rb[w] = w == (base >> 5) ? padword : 0u;
+  if (t == 0) b.row_raw[r] = (base + 7) / 8;
+}
+
+// every block's bits into its row's buffer at its offset: a lane per block again
+__global__ __launch_bounds__(256) void k_jpg_bits(JpgBufs b, uint32_t nblk, int nbr, int bpm, int nluma) {
+  __shared__ uint32_t s_tab[kJpgTabWords];
+  for (int i = threadIdx.x; i < kJpgTabWords; i += 256) s_tab[i] = b.tab[i];
+  __syncthreads();
+  const uint32_t blk = blockIdx.x * 256 + threadIdx.x;
+  if (blk >= nblk) return;
+  const JpgBlockRef ref = jpg_block_ref(b, s_tab, blk, nbr, bpm, nluma);
+  JpgBitWriter bw(b.bits + (size_t)(blk / (uint32_t)nbr) * b.row_words, b.blen[blk]);
+  jpg_walk_block(ref.zz, ref.pred, ref.dc, ref.ac, [&](uint32_t bits, int l) { bw.put(bits, l); });
+  bw.finish();
+}
+
+// one workgroup per MCU row: the row's FF bytes, what stuffing adds to its length
+__global__ __launch_bounds__(256) void k_jpg_ff(JpgBufs b) {
+  __shared__ uint32_t s_tmp[4];
+  const uint32_t r = blockIdx.x;
+  const uint32_t* rb = b.bits + (size_t)r * b.row_words;
+  const uint32_t nbytes = b.row_raw[r];
+  uint32_t nff = 0;
+  for (uint32_t w = threadIdx.x; w * 4 < nbytes; w += 256) {
+    uint32_t v = rb[w];
+    const uint32_t left = nbytes - w * 4;
+    if (left < 4) v &= (1u << (8 * left)) - 1u;  // (the bytes behind the stream are zero anyway)
+    nff += jpg_count_ff(v);
+  }
+  nff = block_reduce(nff, AddOp(), s_tmp, 4);
+  if (threadIdx.x == 0) b.row_len[r] = nbytes + nff;
+}
+
+// Row r's segment to its place in the stream: behind the segments of the rows before it,
+// each followed by its two marker bytes.  A thread takes 16 bytes of the row at a time,
+// counts what it will write (its bytes and a 00 after every FF), a workgroup scan places it.
+__global__ __launch_bounds__(256) void k_jpg_pack(JpgBufs b, int rows) {
+  __shared__ uint32_t s_tmp[4];
+  const int t = threadIdx.x;
+  const uint32_t r = blockIdx.x;
+  uint32_t off = 0;
+  for (uint32_t i = t; i < r; i += 256) off += b.row_len[i] + 2;
+  off = block_reduce(off, AddOp(), s_tmp, 4);
+  const uint32_t nbytes = b.row_raw[r];
+  const uint4* rb = reinterpret_cast<const uint4*>(b.bits + (size_t)r * b.row_words);
+  uint8_t* out = b.out + off;
+  uint32_t done = 0;
+  for (uint32_t c0 = 0; c0 * 16 < nbytes; c0 += 256) {
+    const uint32_t i = c0 + t;
+    uint32_t u[4] = {0, 0, 0, 0};
+    uint32_t valid = 0;
+    if (i * 16 < nbytes) {
+      const uint4 v = rb[i];
+      u[0] = v.x; u[1] = v.y; u[2] = v.z; u[3] = v.w;
+      valid = min(16u, nbytes - i * 16);
+    }
+    uint32_t mine = valid;
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+      if ((uint32_t)k < valid && ((u[k >> 2] >> (8 * (k & 3))) & 0xffu) == 0xffu) mine++;
+    uint32_t total;
+    uint8_t* o = out + done + (block_incl_scan(mine, s_tmp, &total, 4) - mine);
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+      if ((uint32_t)k < valid) {
+        const uint32_t byte = (u[k >> 2] >> (8 * (k & 3))) & 0xffu;
+        *o++ = (uint8_t)byte;
+        if (byte == 0xffu) *o++ = 0;
+      }
+    done += total;
+  }
+  if (t == 0) {
+    out[done] = 0xff;
+    const bool last = r + 1 == (uint32_t)rows;
+    out[done + 1] = last ? 0xd9 : (uint8_t)(0xd0 + (r & 7));
+    if (last) *b.total = off + done + 2;
+  }
+}
+
+// bgr: one BGR8 image of W x H (multiples of 8, a geometry jpg_geom accepts), 8-byte
+// aligned; leaves the entropy-coded data in b.out and its length in *b.total
+hipError_t launch_jpg_encode(const uint8_t* bgr, int W, int H, int quality, int sampling, const JpgBufs& b,
+                             hipStream_t st) {
+  JpgGeom g;
+  if (!jpg_geom(W, H, sampling, &g)) return hipErrorInvalidValue;
+  const int nbr = g.mcux * g.bpm;
+  const uint32_t nblk = (uint32_t)nbr * (uint32_t)g.mcuy;
+  if (b.row_words < (size_t)nbr * (kJpgBlockBytes / 4) + 4) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_jpg_fdct, dim3((nblk + kMjpgBlocksPerWg - 1) / kMjpgBlocksPerWg), dim3(256), 0, st, bgr, b.coef,
+                     W, H, sampling, quality, nblk);
+  const int nluma = g.hs * g.vs;
+  hipLaunchKernelGGL(k_jpg_len, dim3((nblk + 255) / 256), dim3(256), 0, st, b, nblk, nbr, g.bpm, nluma);
+  hipLaunchKernelGGL(k_jpg_rows, dim3(g.mcuy), dim3(kJpgRowThreads), 0, st, b, nbr);
+  hipLaunchKernelGGL(k_jpg_bits, dim3((nblk + 255) / 256), dim3(256), 0, st, b, nblk, nbr, g.bpm, nluma);
+  hipLaunchKernelGGL(k_jpg_ff, dim3(g.mcuy), dim3(256), 0, st, b);
+  hipLaunchKernelGGL(k_jpg_pack, dim3(g.mcuy), dim3(256), 0, st, b, g.mcuy);
+  return hipGetLastError();
+}
+
 static size_t merge_lds_bytes(const Geom& g) { return (size_t)g.merge_lds; }
 
 // one-time kernel attributes: k_ccl_merge's dynamic LDS beyond the default limit.  The

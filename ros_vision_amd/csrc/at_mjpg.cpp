@@ -597,3 +597,216 @@ extern "C" int at_mjpg_stream_mode_host(const uint8_t* jpg, size_t len, int want
   if (stream_bytes) *stream_bytes = dec.packed_bytes();
   return dec.dense() ? 1 : 0;
 }
+
+// ---- JPEG output: tables, header and the sequential host encoder ------------------------
+namespace at {
+namespace {
+
+constexpr uint8_t kJpgQBase[2][64] = {AT_JPG_QBASE_LUMA, AT_JPG_QBASE_CHROMA};
+
+// T.81 Annex C code assignment of one table into code | length << 16 per symbol
+void jpg_huff_table(const uint8_t bits[16], const uint8_t* vals, uint32_t* tab, int nsym) {
+  for (int i = 0; i < nsym; i++) tab[i] = 0;
+  uint32_t code = 0;
+  int k = 0;
+  for (int l = 1; l <= 16; l++) {
+    for (int i = 0; i < bits[l - 1]; i++, k++, code++) tab[vals[k]] = code | ((uint32_t)l << 16);
+    code <<= 1;
+  }
+}
+
+size_t put_segment(uint8_t* p, uint8_t marker, const uint8_t* body, size_t n) {
+  p[0] = 0xff;
+  p[1] = marker;
+  p[2] = (uint8_t)((n + 2) >> 8);
+  p[3] = (uint8_t)(n + 2);
+  memcpy(p + 4, body, n);
+  return n + 4;
+}
+
+// one sample of component c (0 Y, 1 Cb, 2 Cr) of the picture as libjpeg sees it in front of
+// the DCT: (x, y) in the component's own plane, which for chroma runs on past the real
+// samples -- the last input column repeated before the downsampling, the last downsampled
+// row after it
+int32_t jpg_sample(const uint8_t* bgr, int w, const JpgGeom& g, int c, int x, int y) {
+  auto px = [&](int xx, int yy) {
+    const uint8_t* p = bgr + ((size_t)yy * w + (xx < w ? xx : w - 1)) * 3;
+    return mjpg_ycc(c, p[2], p[1], p[0]);
+  };
+  if (c == 0 || g.hs == 1) return px(x, y);
+  if (y > g.ch - 1) y = g.ch - 1;
+  if (g.vs == 1) return mjpg_down_h2v1(px(2 * x, y), px(2 * x + 1, y), x);
+  return mjpg_down_h2v2(px(2 * x, 2 * y), px(2 * x + 1, 2 * y), px(2 * x, 2 * y + 1), px(2 * x + 1, 2 * y + 1), x);
+}
+
+// forward DCT and quantisation of the block at (bx, by) of component c's plane: 64 values
+// in zig-zag order
+void jpg_block(const uint8_t* bgr, int w, const JpgGeom& g, int c, int bx, int by, const uint16_t* q, int16_t* zz) {
+  int32_t ws[64];
+  for (int r = 0; r < 8; r++) {
+    int32_t v[8];
+    for (int k = 0; k < 8; k++) v[k] = jpg_sample(bgr, w, g, c, bx * 8 + k, by * 8 + r) - 128;
+    mjpg_fdct_1d<0>(v);
+    for (int k = 0; k < 8; k++) ws[r * 8 + k] = v[k];
+  }
+  for (int k = 0; k < 8; k++) {
+    int32_t v[8];
+    for (int r = 0; r < 8; r++) v[r] = ws[r * 8 + k];
+    mjpg_fdct_1d<1>(v);
+    for (int r = 0; r < 8; r++) ws[r * 8 + k] = mjpg_quantise(v[r], q[r * 8 + k]);
+  }
+  for (int k = 0; k < 64; k++) zz[k] = (int16_t)ws[kZigzag[k]];
+}
+
+// entropy-coded segment writer: MSB first, FF -> FF 00
+struct BitWriter {
+  std::vector<uint8_t>* out;
+  uint64_t acc = 0;
+  int cnt = 0;
+  void byte(uint8_t b) {
+    out->push_back(b);
+    if (b == 0xff) out->push_back(0);
+  }
+  void put(uint32_t code, int len) {  // len <= 32
+    acc = (acc << len) | code;
+    cnt += len;
+    while (cnt >= 8) {
+      byte((uint8_t)(acc >> (cnt - 8)));
+      cnt -= 8;
+    }
+  }
+  void flush() {  // pad with 1-bits to a byte
+    if (cnt) put((1u << (8 - cnt)) - 1u, 8 - cnt);
+    acc = 0;
+  }
+};
+
+void jpg_code_block(BitWriter& bw, const int16_t* zz, int pred, const uint32_t* dc, const uint32_t* ac) {
+  const int diff = zz[0] - pred;
+  int n = mjpg_nbits(diff, 11);
+  bw.put(dc[n] & 0xffffu, (int)(dc[n] >> 16));
+  if (n) bw.put((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << n) - 1u), n);
+  int run = 0;
+  for (int k = 1; k < 64; k++) {
+    const int v = zz[k];
+    if (!v) {
+      run++;
+      continue;
+    }
+    for (; run > 15; run -= 16) bw.put(ac[0xf0] & 0xffffu, (int)(ac[0xf0] >> 16));
+    n = mjpg_nbits(v, 10);
+    const uint32_t e = ac[(run << 4) | n];
+    bw.put(e & 0xffffu, (int)(e >> 16));
+    bw.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << n) - 1u), n);
+    run = 0;
+  }
+  if (run) bw.put(ac[0] & 0xffffu, (int)(ac[0] >> 16));
+}
+
+}  // namespace
+
+void jpg_huff_tables(uint32_t* tab) {
+  jpg_huff_table(kStdDcLumBits, kStdDcVals, tab, kJpgDcTab);
+  jpg_huff_table(kStdDcChrBits, kStdDcVals, tab + kJpgDcTab, kJpgDcTab);
+  jpg_huff_table(kStdAcLumBits, kStdAcLumVals, tab + 2 * kJpgDcTab, kJpgAcTab);
+  jpg_huff_table(kStdAcChrBits, kStdAcChrVals, tab + 2 * kJpgDcTab + kJpgAcTab, kJpgAcTab);
+}
+
+size_t jpg_write_header(uint8_t* dst, int w, int h, int quality, int sampling) {
+  JpgGeom g;
+  if (!jpg_geom(w, h, sampling, &g)) return 0;
+  uint8_t* p = dst;
+  *p++ = 0xff;
+  *p++ = 0xd8;
+  static const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+  p += put_segment(p, 0xe0, jfif, sizeof(jfif));
+  for (int t = 0; t < 2; t++) {
+    uint8_t body[65];
+    body[0] = (uint8_t)t;
+    for (int k = 0; k < 64; k++) body[1 + k] = (uint8_t)mjpg_quant_entry(kJpgQBase[t][kZigzag[k]], quality);
+    p += put_segment(p, 0xdb, body, sizeof(body));
+  }
+  const uint8_t sof[15] = {8, (uint8_t)(h >> 8), (uint8_t)h, (uint8_t)(w >> 8), (uint8_t)w, 3,
+                           1, (uint8_t)((g.hs << 4) | g.vs), 0, 2, 0x11, 1, 3, 0x11, 1};
+  p += put_segment(p, 0xc0, sof, sizeof(sof));
+  const struct {
+    uint8_t id;
+    const uint8_t* bits;
+    const uint8_t* vals;
+    int n;
+  } dht[4] = {{0x00, kStdDcLumBits, kStdDcVals, 12}, {0x10, kStdAcLumBits, kStdAcLumVals, 162},
+              {0x01, kStdDcChrBits, kStdDcVals, 12}, {0x11, kStdAcChrBits, kStdAcChrVals, 162}};
+  for (const auto& t : dht) {
+    uint8_t body[17 + 162];
+    body[0] = t.id;
+    memcpy(body + 1, t.bits, 16);
+    memcpy(body + 17, t.vals, (size_t)t.n);
+    p += put_segment(p, 0xc4, body, 17 + (size_t)t.n);
+  }
+  const uint8_t dri[2] = {(uint8_t)(g.mcux >> 8), (uint8_t)g.mcux};
+  p += put_segment(p, 0xdd, dri, sizeof(dri));
+  static const uint8_t sos[10] = {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
+  p += put_segment(p, 0xda, sos, sizeof(sos));
+  return (size_t)(p - dst);
+}
+
+size_t jpg_max_bytes(int w, int h, int sampling) {
+  JpgGeom g;
+  if (!jpg_geom(w, h, sampling, &g)) return 0;
+  // per MCU row: its blocks at their worst, doubled by stuffing, and RSTm or EOI
+  return kJpgHeaderMax + (size_t)g.mcuy * (2 * (size_t)g.mcux * g.bpm * kJpgBlockBytes + 2);
+}
+
+}  // namespace at
+
+extern "C" size_t at_jpeg_max_bytes(int width, int height, int sampling) {
+  return at::jpg_max_bytes(width, height, sampling);
+}
+
+extern "C" int at_jpeg_encode_host(const uint8_t* bgr, int w, int h, int quality, int sampling, uint8_t* out,
+                                   size_t cap, size_t* len) {
+  using namespace at;
+  if (len) *len = 0;
+  JpgGeom g;
+  if (!bgr || !out || !len || quality < 1 || quality > 100 || !jpg_geom(w, h, sampling, &g)) return kMjpgInvalid;
+  uint16_t q[2][64];
+  for (int t = 0; t < 2; t++)
+    for (int k = 0; k < 64; k++) q[t][k] = (uint16_t)mjpg_quant_entry(kJpgQBase[t][k], quality);
+  uint32_t tab[kJpgTabWords];
+  jpg_huff_tables(tab);
+  const uint32_t* dc[2] = {tab, tab + kJpgDcTab};
+  const uint32_t* ac[2] = {tab + 2 * kJpgDcTab, tab + 2 * kJpgDcTab + kJpgAcTab};
+  std::vector<uint8_t> s(kJpgHeaderMax);
+  s.resize(jpg_write_header(s.data(), w, h, quality, sampling));
+  BitWriter bw{&s};
+  int16_t zz[64];
+  for (int my = 0; my < g.mcuy; my++) {
+    int pred[3] = {0, 0, 0};
+    for (int mx = 0; mx < g.mcux; mx++) {
+      int last_dc = 0;  // quantised DC of the luma block before, inside this MCU
+      for (int k = 0; k < g.hs * g.vs; k++) {
+        const int bx = mx * g.hs + k % g.hs, by = my * g.vs + k / g.hs;
+        if (bx < g.bw && by < g.bh) {
+          jpg_block(bgr, w, g, 0, bx, by, q[0], zz);
+        } else {  // a dummy block beyond the picture
+          memset(zz, 0, sizeof(zz));
+          zz[0] = (int16_t)last_dc;
+        }
+        jpg_code_block(bw, zz, pred[0], dc[0], ac[0]);
+        pred[0] = last_dc = zz[0];
+      }
+      for (int c = 1; c < 3; c++) {
+        jpg_block(bgr, w, g, c, mx, my, q[1], zz);
+        jpg_code_block(bw, zz, pred[c], dc[1], ac[1]);
+        pred[c] = zz[0];
+      }
+    }
+    bw.flush();
+    s.push_back(0xff);
+    s.push_back(my + 1 < g.mcuy ? (uint8_t)(0xd0 + (my & 7)) : (uint8_t)0xd9);
+  }
+  *len = s.size();
+  if (s.size() > cap) return -3;  // AT_E_CAPACITY: *len is what the stream needs
+  memcpy(out, s.data(), s.size());
+  return kMjpgOk;
+}

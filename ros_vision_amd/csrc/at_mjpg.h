@@ -148,6 +148,137 @@ AT_MJPG_HD uint32_t mjpg_bgr(int32_t y, int32_t cb, int32_t cr) {
   return (uint32_t)b | ((uint32_t)g << 8) | ((uint32_t)r << 16);
 }
 
+// ---- JPEG output (at_jpeg_encode_host, k_jpg_fdct ... k_jpg_pack) -----------------------
+// The forward half, libjpeg's integer "slow" path again, shared by the host encoder and the
+// kernels so that both produce libjpeg's bytes.
+//
+// libjpeg's RGB -> YCbCr (jccolor.c: 16-bit fixed point), component c of one pixel, 0..255:
+//   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+//   Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+//   Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+// (the constants selected, not three branches: lanes of one wave convert different components)
+AT_MJPG_HD int32_t mjpg_ycc(int c, int32_t r, int32_t g, int32_t b) {
+  const int32_t kr = c == 0 ? 19595 : (c == 1 ? -11059 : 32768);
+  const int32_t kg = c == 0 ? 38470 : (c == 1 ? -21709 : -27439);
+  const int32_t kb = c == 0 ? 7471 : (c == 1 ? 32768 : -5329);
+  const int32_t off = c == 0 ? 32768 : (128 << 16) + 32767;
+  return (kr * r + kg * g + kb * b + off) >> 16;
+}
+// libjpeg's chroma downsampling (jcsample.c), one output sample of output column `col`:
+// 4:2:0 (h2v2) over a 2 x 2 square, the bias alternating 1, 2; 4:2:2 (h2v1) over a pair, 0, 1
+AT_MJPG_HD int32_t mjpg_down_h2v2(int32_t a, int32_t b, int32_t c, int32_t d, int col) {
+  return (a + b + c + d + 1 + (col & 1)) >> 2;
+}
+AT_MJPG_HD int32_t mjpg_down_h2v1(int32_t a, int32_t b, int col) { return (a + b + (col & 1)) >> 1; }
+
+// One 1-D pass of libjpeg's integer "slow" forward DCT (jfdctint: the constants of
+// mjpg_idct_1d, 2 pass bits) on 8 values in place.  PASS 0 is the row pass (results scaled
+// up by 4), PASS 1 the column pass that follows it (the block ends scaled by 8).
+template <int PASS>
+AT_MJPG_HD void mjpg_fdct_1d(int32_t (&v)[8]) {
+  constexpr int kShift = PASS == 0 ? 11 : 15;  // CONST_BITS -/+ PASS1_BITS
+  constexpr int32_t kRnd = 1 << (kShift - 1);
+  const int32_t t0 = v[0] + v[7], t7 = v[0] - v[7], t1 = v[1] + v[6], t6 = v[1] - v[6];
+  const int32_t t2 = v[2] + v[5], t5 = v[2] - v[5], t3 = v[3] + v[4], t4 = v[3] - v[4];
+  const int32_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  if (PASS == 0) {
+    v[0] = (t10 + t11) * 4;
+    v[4] = (t10 - t11) * 4;
+  } else {
+    v[0] = (t10 + t11 + 2) >> 2;
+    v[4] = (t10 - t11 + 2) >> 2;
+  }
+  int32_t z1 = (t12 + t13) * 4433;                    // FIX(0.541196100)
+  v[2] = (z1 + t13 * 6270 + kRnd) >> kShift;          // FIX(0.765366865)
+  v[6] = (z1 - t12 * 15137 + kRnd) >> kShift;         // FIX(1.847759065)
+  z1 = t4 + t7;
+  int32_t z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+  const int32_t z5 = (z3 + z4) * 9633;                // FIX(1.175875602)
+  const int32_t a4 = t4 * 2446, a5 = t5 * 16819;      // FIX(0.298631336), FIX(2.053119869)
+  const int32_t a6 = t6 * 25172, a7 = t7 * 12299;     // FIX(3.072711026), FIX(1.501321110)
+  z1 *= -7373;                                        // FIX(0.899976223)
+  z2 *= -20995;                                       // FIX(2.562915447)
+  z3 = z3 * -16069 + z5;                              // FIX(1.961570560)
+  z4 = z4 * -3196 + z5;                               // FIX(0.390180644)
+  v[7] = (a4 + z1 + z3 + kRnd) >> kShift;
+  v[5] = (a5 + z2 + z4 + kRnd) >> kShift;
+  v[3] = (a6 + z2 + z3 + kRnd) >> kShift;
+  v[1] = (a7 + z1 + z4 + kRnd) >> kShift;
+}
+
+// libjpeg's quality rule (jpeg_quality_scaling + jpeg_add_quant_table, baseline): the entry
+// of an Annex K base value at quality 1..100
+AT_MJPG_HD int32_t mjpg_quant_entry(int32_t base, int quality) {
+  const int32_t scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+  const int32_t q = (base * scale + 50) / 100;
+  return q < 1 ? 1 : (q > 255 ? 255 : q);
+}
+// the quantiser: a forward DCT result (scaled by 8) by the table entry q, rounded half away
+AT_MJPG_HD int32_t mjpg_quantise(int32_t c, int32_t q) {
+  const int32_t d = 8 * q, a = c < 0 ? -c : c;
+  const int32_t m = (a + (d >> 1)) / d;
+  return c < 0 ? -m : m;
+}
+// magnitude category of a coefficient or DC difference, at most `most` (10 for AC, 11 for DC:
+// 8-bit samples give no more; the clamp makes the bound hold for the buffers' sake whatever
+// the arithmetic gave)
+AT_MJPG_HD int mjpg_nbits(int32_t v, int most) {
+  const uint32_t a = (uint32_t)(v < 0 ? -v : v);
+  const int n = a ? 32 - __builtin_clz(a) : 0;
+  return n > most ? most : n;
+}
+
+// Annex K.1 base quantisation tables, natural (row-major) order
+#define AT_JPG_QBASE_LUMA                                                                         \
+  {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  \
+   69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55, 64,  \
+   81, 104, 113, 92, 49, 64,  78,  87,  103, 121, 120, 101, 72, 92,  95,  98,  112, 100, 103, 99}
+#define AT_JPG_QBASE_CHROMA                                                                       \
+  {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, \
+   47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, \
+   99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}
+
+// sampling codes of the C ABI (AT_JPEG_420 ...)
+constexpr int kJpg420 = 0, kJpg422 = 1, kJpg444 = 2;
+// Most bits one block can take: a DC code of at most 11 bits with 11 magnitude bits, 63 AC
+// codes of at most 16 bits with 10 magnitude bits each (1660); the buffers give every block
+// 208 bytes.  Byte stuffing at most doubles a segment.
+constexpr int kJpgBlockBytes = 208;
+static_assert(22 + 63 * 26 <= 8 * kJpgBlockBytes, "a block's worst case fits its share");
+
+// Geometry of the output stream for a w x h picture (multiples of 8) at a sampling.
+struct JpgGeom {
+  int hs, vs;        // luma sampling factors
+  int bw, bh;        // luma block grid (w / 8, h / 8)
+  int mcux, mcuy;    // MCU grid; one restart interval = one MCU row
+  int bpm;           // blocks per MCU: hs * vs + 2
+  int cw, ch;        // real chroma samples (w / hs, h / vs)
+};
+AT_MJPG_HD bool jpg_geom(int w, int h, int sampling, JpgGeom* g) {
+  if (w < 8 || h < 8 || (w & 7) || (h & 7) || w > 65528 || h > 65528) return false;
+  if (sampling != kJpg420 && sampling != kJpg422 && sampling != kJpg444) return false;
+  g->hs = sampling == kJpg444 ? 1 : 2;
+  g->vs = sampling == kJpg420 ? 2 : 1;
+  g->bw = w / 8;
+  g->bh = h / 8;
+  g->mcux = (g->bw + g->hs - 1) / g->hs;
+  g->mcuy = (g->bh + g->vs - 1) / g->vs;
+  g->bpm = g->hs * g->vs + 2;
+  g->cw = w / g->hs;
+  g->ch = h / g->vs;
+  return true;
+}
+
+// The four Annex K Huffman tables as encoder tables: entry = code | length << 16 for symbol s
+// of table [0] DC luma, [1] DC chroma (16 entries each), [2] AC luma, [3] AC chroma (256 each).
+constexpr int kJpgDcTab = 16, kJpgAcTab = 256, kJpgTabWords = 2 * kJpgDcTab + 2 * kJpgAcTab;
+void jpg_huff_tables(uint32_t* tab /* kJpgTabWords */);
+// The stream's header (SOI .. SOS) into dst (cap >= kJpgHeaderMax); returns its length.
+constexpr size_t kJpgHeaderMax = 1024;
+size_t jpg_write_header(uint8_t* dst, int w, int h, int quality, int sampling);
+// A capacity no stream of this geometry exceeds (0: bad geometry).
+size_t jpg_max_bytes(int w, int h, int sampling);
+
 // What the marker parser found.
 struct MjpgInfo {
   int width, height;
@@ -235,5 +366,13 @@ extern "C" int at_mjpg_decode_bgr_host(const uint8_t* jpg, size_t len, uint8_t* 
 // (0 x 0: any size): 0 sparse, 1 dense, < 0 the error at_enqueue_mjpg would give
 extern "C" int at_mjpg_stream_mode_host(const uint8_t* jpg, size_t len, int want_w, int want_h,
                                         size_t* stream_bytes);
+
+// Host-only baseline JPEG encoder (the CPU reference of the GPU encoder): BGR8 [h][w][3],
+// w and h multiples of 8, quality 1..100, sampling kJpg420 / kJpg422 / kJpg444; one restart
+// interval per MCU row.  Writes the whole file; *len receives its size, also when it does
+// not fit cap (then -3, AT_E_CAPACITY, and nothing is written).
+extern "C" int at_jpeg_encode_host(const uint8_t* bgr, int w, int h, int quality, int sampling, uint8_t* out,
+                                   size_t cap, size_t* len);
+extern "C" size_t at_jpeg_max_bytes(int width, int height, int sampling);
 
 #endif  // AT_MJPG_H_

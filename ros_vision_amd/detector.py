@@ -38,7 +38,9 @@ EXPORTS = [
     "at_enqueue_mjpg", "at_detect_mjpg", "at_detect_mjpg_batch", "at_mjpg_set_threads", "at_mjpg_stats",
     "at_mjpg_decode_gray_host", "at_mjpg_stream_mode_host",
     "at_mjpg_set_color", "at_mjpg_bgr", "at_mjpg_copy_bgr", "at_mjpg_decode_bgr_host",
+    "at_encode_jpeg_device", "at_annotate_jpeg", "at_jpeg_max_bytes", "at_jpeg_stats", "at_jpeg_encode_host",
 ]
+JPEG_SAMPLINGS = {"4:2:0": 0, "4:2:2": 1, "4:4:4": 2}  # AT_JPEG_420 / 422 / 444
 
 TAG_SIZE = 0.1651  # metres, apriltags_cuda_detector.hpp:39
 
@@ -217,6 +219,19 @@ def load_library(path: str = LIB_PATH):
         L.at_mjpg_copy_bgr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.at_mjpg_decode_bgr_host.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
                                               C.POINTER(C.c_int)]
+    if hasattr(L, "at_annotate_jpeg"):  # (A/B builds of older sources lack the JPEG output)
+        L.at_encode_jpeg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                            C.POINTER(C.c_size_t)]
+        L.at_annotate_jpeg.argtypes = [C.c_void_p, C.c_int, C.POINTER(AtDetection), C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.at_jpeg_max_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.at_jpeg_max_bytes.restype = C.c_size_t
+        L.at_jpeg_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.at_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
+        L.at_host_free.argtypes = [C.c_void_p]
+        L.at_host_free.restype = None
+        L.at_jpeg_encode_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                          C.POINTER(C.c_size_t)]
     _LIB = L
     return L
 
@@ -262,6 +277,46 @@ def mjpg_decode_bgr(jpg: bytes):
     if rc < 0:
         raise MjpgError("at_mjpg_decode_bgr_host", rc)
     return out
+
+
+class JpegError(RuntimeError):
+    """A JPEG encode the library refused: `code` is AT_E_INVALID (quality, sampling, size,
+    gating) or AT_E_CAPACITY (then `needed` is the stream's size)."""
+
+    def __init__(self, what, code, needed=0):
+        super().__init__("%s failed: %s (%d)" % (what, load_library().at_strerror(code).decode(), code))
+        self.code, self.needed = code, needed
+
+
+def _jpeg_sampling(sampling):
+    if sampling not in JPEG_SAMPLINGS:
+        raise JpegError("JPEG encode (sampling %r)" % (sampling,), AT_E_INVALID)
+    return JPEG_SAMPLINGS[sampling]
+
+
+def jpeg_max_bytes(width: int, height: int, sampling="4:2:0"):
+    """at_jpeg_max_bytes: a capacity no JPEG of this geometry exceeds."""
+    return int(load_library().at_jpeg_max_bytes(int(width), int(height), _jpeg_sampling(sampling)))
+
+
+def jpeg_encode_host(bgr, quality=95, sampling="4:2:0", cap=None):
+    """at_jpeg_encode_host: the BGR8 image (H, W, 3), H and W multiples of 8, as a baseline
+    JPEG (bytes), encoded on the host with the arithmetic the encode kernels run (no device
+    needed): byte for byte libjpeg's stream with one restart interval per MCU row."""
+    L = load_library()
+    bgr = np.ascontiguousarray(bgr, np.uint8)
+    if bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise JpegError("at_jpeg_encode_host", AT_E_INVALID)
+    h, w = bgr.shape[:2]
+    s = _jpeg_sampling(sampling)
+    if cap is None:
+        cap = int(L.at_jpeg_max_bytes(w, h, s))
+    out = np.empty(max(int(cap), 1), np.uint8)
+    n = C.c_size_t()
+    rc = L.at_jpeg_encode_host(bgr.ctypes.data, w, h, int(quality), s, out.ctypes.data, int(cap), C.byref(n))
+    if rc < 0:
+        raise JpegError("at_jpeg_encode_host", rc, n.value)
+    return out[:n.value].tobytes()
 
 
 def mjpg_stream_mode(jpg: bytes, width: int = 0, height: int = 0):
@@ -375,6 +430,9 @@ class GpuDetector:
         if getattr(self, "_h", None):
             load_library().at_destroy(self._h)
             self._h = None
+        if getattr(self, "_jpeg_buf", None) is not None:
+            load_library().at_host_free(self._jpeg_buf)
+            self._jpeg_buf = None
 
     def __del__(self):
         self.close()
@@ -624,6 +682,56 @@ class GpuDetector:
         out = np.empty((self.height, self.width, 3), np.uint8)
         _check(load_library().at_annotate_staged(self._h, frame, arr, n, out.ctypes.data), "at_annotate_staged")
         return out
+
+    # ---- the annotated image as a JPEG, encoded on the GPU -----------------------
+    def _jpeg_out(self, sampling, cap):
+        """(code, capacity, buffer): a page-locked buffer of the worst-case size, allocated
+        once per detector (at_host_alloc: the stream's bytes arrive by DMA)."""
+        s = _jpeg_sampling(sampling)
+        L = load_library()
+        if getattr(self, "_jpeg_buf", None) is None:
+            self._jpeg_cap = max(int(L.at_jpeg_max_bytes(self.width, self.height, k)) for k in (0, 1, 2))
+            if not self._jpeg_cap:
+                raise JpegError("at_jpeg_max_bytes", AT_E_INVALID)
+            p = C.c_void_p()
+            _check(L.at_host_alloc(self._jpeg_cap, C.byref(p)), "at_host_alloc")
+            self._jpeg_buf = p
+        return s, (self._jpeg_cap if cap is None else min(int(cap), self._jpeg_cap))
+
+    def _jpeg_result(self, rc, what, n):
+        if rc in (AT_E_INVALID, AT_E_CAPACITY):
+            raise JpegError(what, rc, n.value)
+        _check(rc, what)
+        return C.string_at(self._jpeg_buf, n.value)
+
+    def encode_jpeg_device(self, bgr_ptr: int, quality=95, sampling="4:2:0", cap=None):
+        """at_encode_jpeg_device: the device-resident BGR8 image at `bgr_ptr` (width x height
+        x 3) as a baseline JPEG (bytes), encoded on the GPU.  `cap` limits the accepted size
+        (JpegError with code AT_E_CAPACITY and `needed` beyond it)."""
+        s, cap = self._jpeg_out(sampling, cap)
+        n = C.c_size_t()
+        rc = load_library().at_encode_jpeg_device(self._h, C.c_void_p(bgr_ptr), int(quality), s, self._jpeg_buf,
+                                                  cap, C.byref(n))
+        return self._jpeg_result(rc, "at_encode_jpeg_device", n)
+
+    def annotate_jpeg(self, frame=0, quality=95, sampling="4:2:0", cap=None):
+        """at_annotate_jpeg: annotate_staged's image as a baseline JPEG (bytes): drawn and
+        encoded on the GPU, only the compressed bytes cross the link."""
+        # (a frame index no batch can have: the library refuses it)
+        arr, nd = self._records_array(frame) if 0 <= frame < self.max_batch else ((AtDetection * 1)(), 0)
+        s, cap = self._jpeg_out(sampling, cap)
+        n = C.c_size_t()
+        rc = load_library().at_annotate_jpeg(self._h, frame, arr, nd, int(quality), s, self._jpeg_buf, cap,
+                                             C.byref(n))
+        return self._jpeg_result(rc, "at_annotate_jpeg", n)
+
+    JPEG_STATS = ("bytes", "encode_kernels_ns")
+
+    def jpeg_stats(self):
+        """at_jpeg_stats of the last encode."""
+        buf = (C.c_uint64 * len(self.JPEG_STATS))()
+        n = _check(load_library().at_jpeg_stats(self._h, buf, len(buf)), "at_jpeg_stats")
+        return dict(zip(self.JPEG_STATS, [int(x) for x in buf[:n]]))
 
     def frame_status(self, frame=0):
         return load_library().at_frame_status(self._h, frame)

@@ -119,13 +119,14 @@ class FrameResult:
     networktables_pose_data: list = field(default_factory=list)      # [t, id, x, y, z] * n
     proto_tags: list = field(default_factory=list)                    # ApriltagListProto.tags
     image: np.ndarray = None
+    image_jpeg: bytes = None                                          # image_jpeg set: the image as JPEG instead
 
 
 class ApriltagsDetectorNode:
     """ApriltagsDetector (apriltags_cuda_detector.cu) without the ROS transport."""
 
     def __init__(self, width, height, parameters=None, calibration_dir=None, system_config_path=None,
-                 publishers=None, device=0, mjpg_color=False):
+                 publishers=None, device=0, mjpg_color=False, image_jpeg=None):
         self.params = dict(PARAMETER_DEFAULTS)
         self.params.update(parameters or {})
         serial = self.params["camera_serial"]
@@ -146,6 +147,13 @@ class ApriltagsDetectorNode:
         self.pose_topic = self.params["publish_pose_to_topic"]
         self.camera_pose_topic = self.pose_topic + "_camera"
         self.image_topic = self.params["publish_images_to_topic"]
+        # image_jpeg = <quality 1..100>: the annotated image is drawn and JPEG-encoded on the GPU
+        # (at_annotate_jpeg, 4:2:0 as cv::imencode writes) and published as bytes on the
+        # compressed topic, the one the bag recording and the viewer read, instead of raw
+        self.image_jpeg = None if image_jpeg is None else int(image_jpeg)
+        if self.image_jpeg is not None and not 1 <= self.image_jpeg <= 100:
+            raise ValueError("image_jpeg is a JPEG quality, 1..100")
+        self.compressed_image_topic = self.image_topic + "/compressed"
         self.csv = None
         if self.params["measurement_mode"]:
             path = self.params["timing_csv_path"] or time.strftime("apriltags_timing_%Y%m%d_%H%M%S.csv")
@@ -171,7 +179,8 @@ class ApriltagsDetectorNode:
         the GPU, poses and tables come out as for the other encodings.  An annotated
         image is published for it only with mjpg_color=True: the frame's colour is then
         decoded on the GPU too and outlined there (at_annotate_staged); otherwise there is
-        no colour image to draw on."""
+        no colour image to draw on.  With image_jpeg set, whichever image there is goes out
+        as JPEG bytes on `<publish_images_to_topic>/compressed` and the raw topic is silent."""
         start = time.perf_counter()
         latency_s = (receive_time_s if receive_time_s is not None else time.time()) - stamp_s
         det0 = time.perf_counter()
@@ -189,9 +198,12 @@ class ApriltagsDetectorNode:
             res.proto_tags.append({"collect_time": stamp_s, "tag_id": tag.id, "x": rx, "y": ry, "z": rz})
             res.tag_detection_camera_array.append((tag.id, *(float(v) for v in tag.camera)))
             res.tag_detection_array.append((tag.id, rx, ry, rz))
-        if encoding == "bgr8":
+        has_image = encoding == "bgr8" or (encoding == "jpeg" and self.mjpg_color)
+        if has_image and self.image_jpeg is not None:
+            res.image_jpeg = self.detector.annotate_jpeg(0, quality=self.image_jpeg, sampling="4:2:0")
+        elif encoding == "bgr8":
             res.image = draw_detection_outlines(np.array(image, copy=True), dets)
-        elif encoding == "jpeg" and self.mjpg_color:
+        elif has_image:
             res.image = self.detector.annotate_staged(0)
         nt0 = time.perf_counter()
         self._publish("networktables", res.networktables_pose_data)
@@ -203,6 +215,8 @@ class ApriltagsDetectorNode:
         pc1 = time.perf_counter()
         if res.image is not None:
             self._publish(self.image_topic, res.image)
+        if res.image_jpeg is not None:
+            self._publish(self.compressed_image_topic, res.image_jpeg)
         pi1 = time.perf_counter()
         if self.csv:
             us = lambda a, b: int(round((b - a) * 1e6))  # noqa: E731
