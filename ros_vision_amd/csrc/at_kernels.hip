@@ -1593,8 +1593,9 @@ __device__ __forceinline__ void bnd_spill(const DevBufs& b, int f, uint64_t key,
   }
 }
 
-// SGPR budget (experiment builds: -DAT_BND_SGPRS=N): at .sgpr_count 106 a CU admits
-// 6 of these 4-wave workgroups (800 / (112 + 16)); capped at 80 it admits 8 (the
+// SGPR budget (experiment builds: -DAT_BND_SGPRS=N): at .sgpr_count 106 a CU admitted
+// 6 of these 4-wave workgroups (800 / (112 + 16)), at the present 96 it admits 7
+// (profiles/bnd_row_stage/); capped at 80 it admits 8 (the
 // 19.5 KB of LDS allows 8 too): k_boundary 0.250 -> 0.236 ms per 128 frames
 // serialized, but 2 % less concurrent throughput -- eight workgroups take a CU's
 // whole LDS from the other batches' kernels (profiles/r04d/ab_sgpr_caps_stages.txt)
@@ -1640,39 +1641,75 @@ __global__ __launch_bounds__(256) AT_BND_ATTR void k_boundary(DevBufs b, Geom g)
   const uint32_t* par = b.par + fo;
   const int Wd = g.Wd;
   const int ty0 = 1 + bi.y * (4 * kBndRows), tx0 = bi.x * 64;  // halo origin: x0 - 1
-  constexpr int kTR = 4 * kBndRows + 1, kTC = 66, kTN = kTR * kTC;
-  constexpr int kPer = (kTN + 255) / 256;
+  constexpr int kTR = 4 * kBndRows + 1, kTC = 66;
   // label of a pixel = par[par[node]]: its block node (fg -> F, bg -> L / R by
   // column) -> local root -> component root | kept bit (k_ccl_merge / k_ccl_roots;
   // a local root's own word already holds root | kept, so the second hop masks)
   // (the threshold byte and both candidate nodes' parents are loaded together,
   // the byte then picks fg or bg: one round trip fewer than thr -> node -> parent)
+  // Row-mapped: wave w stages halo rows w, w + 4, ... (kBndRows of them), lane l halo
+  // column l.  A row's clamp, its in-image flag and the row parts of the three offsets
+  // are wave-uniform (scalar registers; the wave index goes through readfirstlane so
+  // that the compiler knows), a lane's column parts are computed once: a load is a
+  // scalar row base plus the lane's 32-bit offset.  The last pass takes what is left
+  // -- the last halo row (wave 0) and the two halo columns past the 64th (wave 1, one
+  // element per lane) -- with per-lane rows; waves 2 and 3 skip it.
+  constexpr int kPer = kBndRows + 1;
   uint32_t lv[kPer], lb[kPer];
   uint8_t tv[kPer];
+  const int sw = __builtin_amdgcn_readfirstlane((int)threadIdx.y), sl = (int)threadIdx.x;
+  typedef const __attribute__((address_space(1))) char* gptr;  // (global: no flat loads behind the asm below)
+  const gptr thr_c = (gptr)thr, par_c = (gptr)par;
+  const int Hd = g.Hd, BW3 = 3 * g.BW;
+  const bool xin = tx0 + sl < Wd;
+  const uint32_t xc = (uint32_t)min(tx0 + sl, Wd - 1);
+  const uint32_t oF = (xc >> 1) << 2, oL = xc << 2;  // byte offsets in a row of F words, of L / R words
   // loads from clamped addresses, selected afterwards (no branch per load)
 #pragma unroll
+  for (int k = 0; k < kBndRows; k++) {
+    const int yy = ty0 + sw + 4 * k, yc = min(yy, Hd - 1);
+    const bool in = xin && yy < Hd;
+    const uint32_t rowF = (uint32_t)((yc >> 1) * BW3);
+    // (the row bases pass through scalar registers as they are: added to the lane's
+    // column first they would be 64-bit vector adds per load)
+    gptr pT = thr_c + (uint32_t)(yc * Wd);
+    gptr pF = par_c + ((size_t)rowF << 2);
+    gptr pL = par_c + ((size_t)(rowF + (uint32_t)g.BW) << 2);
+    asm("" : "+s"(pT), "+s"(pF), "+s"(pL));
+    const uint8_t t = *reinterpret_cast<const __attribute__((address_space(1))) uint8_t*>(pT + xc);
+    lv[k] = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(pF + oF);
+    lb[k] = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(pL + oL);
+    tv[k] = in ? t : (uint8_t)127;  // (127 outside the image: the labels are then not looked at)
+  }
+  const bool rest = sw == 0 || (sw == 1 && sl < 2 * kTR);
+  const int erest = sw == 0 ? (kTR - 1) * kTC + sl : (sl >> 1) * kTC + 64 + (sl & 1);  // the element in the tile
+  uint8_t trest = 127;
+  bool inrest = false;
+  lv[kBndRows] = lb[kBndRows] = 0xffffffffu;
+  if (rest) {
+    const int yy = ty0 + (sw == 0 ? kTR - 1 : sl >> 1), xx = tx0 + (sw == 0 ? sl : 64 + (sl & 1));
+    const uint32_t yc = (uint32_t)min(yy, Hd - 1), xr = (uint32_t)min(xx, Wd - 1);
+    // (24-bit multiplies: planes of at most 1024 x 1024)
+    const uint32_t nF = __umul24(yc >> 1, (uint32_t)BW3);
+    trest = *reinterpret_cast<const __attribute__((address_space(1))) uint8_t*>(thr_c + (__umul24(yc, (uint32_t)Wd) + xr));
+    lv[kBndRows] = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(par_c + ((nF + (xr >> 1)) << 2));
+    lb[kBndRows] = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(par_c + ((nF + (uint32_t)g.BW + xr) << 2));
+    inrest = yy < Hd && xx < Wd;
+  }
+  tv[kBndRows] = inrest ? trest : (uint8_t)127;
+#pragma unroll
   for (int k = 0; k < kPer; k++) {
-    const int e = tid + 256 * k, ec = min(e, kTN - 1);  // (lanes past the tile read its last element)
-    const int yy = ty0 + ec / kTC, xx = tx0 + ec % kTC;
-    const bool in = e < kTN && yy < g.Hd && xx < Wd;
-    const int yc = min(yy, g.Hd - 1), xc = min(xx, Wd - 1);
-    const uint32_t F = node_F(g, yc >> 1, xc >> 1), LR = node_L(g, yc >> 1, 0) + (uint32_t)xc;
-    const uint8_t t = thr[(size_t)yc * Wd + xc];
-    const uint32_t a = par[F], c = par[LR];
-    tv[k] = in ? t : (uint8_t)127;
-    lv[k] = in ? a : 0xffffffffu;
-    lb[k] = in ? c : 0xffffffffu;
+    if (k < kBndRows || rest) {
+      const bool none = tv[k] == 127;
+      const uint32_t n = tv[k] == 255 ? lv[k] : lb[k];  // local root | kept
+      const uint32_t r = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(par_c + (none ? 0u : (n & ~kKeptBit) << 2));
+      lv[k] = none ? 0xffffffffu : r;
+    }
   }
 #pragma unroll
   for (int k = 0; k < kPer; k++) {
-    lv[k] = tv[k] == 127 ? 0xffffffffu : (tv[k] == 255 ? lv[k] : lb[k]);
-    const uint32_t r = par[lv[k] != 0xffffffffu ? (lv[k] & ~kKeptBit) : 0u];
-    lv[k] = lv[k] != 0xffffffffu ? r : 0xffffffffu;
-  }
-#pragma unroll
-  for (int k = 0; k < kPer; k++) {
-    const int e = tid + 256 * k;
-    if (e < kTN) {
+    if (k < kBndRows || rest) {
+      const int e = k < kBndRows ? (sw + 4 * k) * kTC + sl : erest;
       const bool kept = lv[k] != 0xffffffffu && (KEPT ? (lv[k] & kKeptBit) != 0 : b.size[fo + lv[k]] >= 25);
       s_tlab[e] = lv[k] & ~kKeptBit;
       s_tthr[e] = kept ? tv[k] : (uint8_t)127;
@@ -1739,17 +1776,30 @@ __global__ __launch_bounds__(256) AT_BND_ATTR void k_boundary(DevBufs b, Geom g)
     // the rare other pairs of a lane one by one
     const bool got = hm != 0;
     const uint32_t rf = (hm & 0xfu) ? rep[0] : rep[1];
-    uint32_t nf = nb[7];
+    // (the neighbour label of the lowest set direction, picked by that bit sign-extended
+    // to a mask: two instructions a direction; 0 without points, where it is not used)
+    const uint32_t low = hm & (0u - hm);
+    uint32_t nf = 0;
 #pragma unroll
-    for (int d = 6; d >= 0; d--) nf = ((hm >> d) & 1) ? nb[d] : nf;
+    for (int d = 0; d < 8; d++) nf |= nb[d] & (uint32_t)__builtin_amdgcn_sbfe((int)low, d, 1);
     uint32_t cnt = 0, xm = 0;
+    // a point is in the first pair (rf, nf) in one orientation only: a point's two labels
+    // are components of opposite colour (v0 + v1 == 255), and fg and bg roots are different
+    // nodes (F; L / R), so a pixel of the first point's pixel's colour can only match
+    // (rf, nf) as (own, neighbour), one of the other colour only as (neighbour, own).
+    // The first pixel, where it has points, is the first point's pixel: its neighbours must
+    // be nf.  The second is that pixel itself (the first without points), of its colour,
+    // or of the other: does its own label match, and which label its neighbours must have.
+    const bool like = !(hm & 0xfu) || b2w[1] == b2w[0];
+    const bool ok1 = rep[1] == (like ? rf : nf);
+    const uint32_t want1 = like ? nf : rf;
+    // (as a direction mask: no test of hm's bits one by one)
+    uint32_t eqm = 0;
 #pragma unroll
-    for (int d = 0; d < 8; d++) {
-      const uint32_t rj = rep[d >> 2];
-      const bool in = (hm >> d) & 1, eq = (rj == rf && nb[d] == nf) || (rj == nf && nb[d] == rf);
-      cnt += in && eq;
-      xm |= (in && !eq) ? 1u << d : 0u;
-    }
+    for (int d = 0; d < 8; d++) eqm |= nb[d] == (d < 4 ? nf : want1) ? 1u << d : 0u;
+    eqm &= ok1 ? 0xffu : 0x0fu;
+    cnt = (uint32_t)__builtin_popcount(hm & eqm);
+    xm = hm & ~eqm;
     // one scan for both: the first-pair counts (low half) and the lane's points (high)
     const uint32_t npts = (uint32_t)__builtin_popcount(hm);
     const uint32_t sc = wave_incl_scan(cnt | (npts << 16), AddOp(), 0u);
