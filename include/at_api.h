@@ -321,6 +321,70 @@ int at_gp_copy(at_detector *d, int frame, float *dst, size_t count);
 int at_gp_preprocess_device(const uint8_t *bgr, int width, int height, float *out, int out_width, int out_height,
                             int channels, void *stream);
 
+/* The game-piece node's output parse (game_piece_detection_node.cu:287-292 over
+ * yolo_detection.h:53-209): what the reference does with the network's output tensor,
+ * one frame being raw[(4 + C) * P] floats -- rows of P: x, y, w, h, score_0 .. score_{C-1}.
+ *   parse_yolov11_output  per prediction the first class holding the maximum score above 0
+ *                         (a NaN never wins; nothing above 0: class 0, confidence 0); the
+ *                         prediction is dropped iff confidence < conf_thr (reference 0.25);
+ *   apply_nms             candidates by descending confidence, equal ones by ascending
+ *                         prediction index (the reference's std::sort leaves ties open;
+ *                         this is what a stable sort gives); an unsuppressed candidate is
+ *                         kept and suppresses every later one of its class with
+ *                         iou > iou_thr (strict; reference 0.45), calculate_iou as written
+ *                         there in float32 (std::max / std::min comparisons, IEEE division);
+ *   scale_detections      x, w by (float)orig_w / (float)model_w, y, h likewise.
+ * Boxes come out in NMS order (descending confidence).  The network itself is the user's
+ * engine: it reads at_gp_tensor's pointer and leaves its output in device memory.
+ *
+ * at_gp_parse_host is that on the host (no device needed, no candidate cap): the CPU
+ * reference, sharing the kernels' arithmetic (csrc/at_gp.h).  *n receives the number of
+ * boxes kept; at most cap are written.
+ *
+ * at_gp_parse_device parses nframes tensors in device memory, frame_stride floats apart, on
+ * the detector's stream, ordered after everything queued so far on `producer_stream` (a
+ * hipStream_t of the same device, the stream the engine ran on; event + stream wait, no
+ * host wait; NULL = the null stream), and returns when the boxes are in `out` (host memory,
+ * frame f's at out + f * cap_per_frame).  n_per_frame[f] = boxes kept (at most cap_per_frame
+ * written); status_per_frame[f] (may be NULL) = 0, or AT_E_CAPACITY for a frame with more
+ * than AT_GP_MAX_CANDIDATES candidates, which yields zero boxes (never a silently different
+ * answer; the other frames are unaffected; the reference reserves 1000, the deployed model
+ * yields a few hundred).  orig_w / orig_h are the detector's geometry.  Nothing is
+ * allocated per call: the buffers are allocated on the first call for max_batch frames.
+ * AT_E_INVALID: a NULL, P < 1, C < 1, nframes outside 1..max_batch,
+ * frame_stride < (4 + C) * P, a non-finite threshold, a model size < 1.
+ *
+ * at_gp_draw_boxes_device draws the boxes' outlines (detection_test.cpp:73-100: corners
+ * truncated to int and clamped to the image, cv::rectangle of thickness 2 as four 2-px
+ * segments, colour by cls % 6: green, orange, blue, yellow, magenta, cyan) onto a
+ * device-resident BGR8 image of the detector's geometry, like at_draw_outlines_device;
+ * pixel-identical to node/at_node.cpp's draw_boxes.  The reference's label text and filled
+ * label background are not drawn (OpenCV's Hershey font is not carried here).
+ * at_gp_parse_stats, the last at_gp_parse_device call: [0] candidates (sum over the frames),
+ * [1] most candidates of one frame, [2] boxes kept, [3] the two kernels' time in
+ * nanoseconds (HIP events; measured while at_set_profiling is on, 0 otherwise). */
+typedef struct { float x, y, w, h, conf; int32_t cls; } at_gp_box;   /* 24 bytes */
+#define AT_GP_MAX_CANDIDATES 4096
+int at_gp_parse_host(const float *raw, int num_predictions, int num_classes,
+                     float conf_thr, float iou_thr, int model_w, int model_h, int orig_w, int orig_h,
+                     at_gp_box *out, int cap, int *n);
+int at_gp_parse_device(at_detector *d, const float *d_raw, size_t frame_stride, int nframes,
+                       int num_predictions, int num_classes, float conf_thr, float iou_thr,
+                       int model_w, int model_h, void *producer_stream,
+                       at_gp_box *out, int cap_per_frame, int *n_per_frame, int *status_per_frame);
+int at_gp_draw_boxes_device(at_detector *d, const at_gp_box *boxes, int n, uint8_t *bgr);
+int at_gp_parse_stats(at_detector *d, uint64_t *out, int cap);
+/* The boxes on the frame a host-fed batch staged in HBM, for a node without device memory of
+ * its own: at_annotate_staged / at_annotate_jpeg with boxes in place of tag outlines (same
+ * gating: AT_E_INVALID unless the last batch was host BGR8 frames or a colour-on MJPG batch and
+ * `frame` one of its frames; the staged image is consumed; same capacity rule for the JPEG).
+ * at_gp_copy_raw copies `count` floats of a tensor in device memory to the host on the
+ * detector's stream (e.g. the tensor of an AT_E_CAPACITY frame, for at_gp_parse_host). */
+int at_gp_annotate_staged(at_detector *d, int frame, const at_gp_box *boxes, int n, uint8_t *bgr_out);
+int at_gp_annotate_jpeg(at_detector *d, int frame, const at_gp_box *boxes, int n, int quality, int sampling,
+                        uint8_t *out, size_t cap, size_t *len);
+int at_gp_copy_raw(at_detector *d, const float *d_raw, float *dst, size_t count);
+
 /* The annotated image on the GPU: the node's outlined frame
  * (apriltag_utils.cu:54-79, drawn on the host with cv::line / cv::putText by
  * apriltags_cuda_detector.cu:514-518) drawn onto a device-resident BGR8 image of

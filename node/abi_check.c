@@ -26,6 +26,7 @@ _Static_assert(sizeof(at_tag_detection) == 72 && offsetof(at_tag_detection, robo
                    offsetof(at_tag_detection, err) == 64,
                "at_tag_detection");
 _Static_assert(sizeof(at_quad_record) == 52 && offsetof(at_quad_record, corners) == 20, "at_quad_record");
+_Static_assert(sizeof(at_gp_box) == 24 && offsetof(at_gp_box, conf) == 16 && offsetof(at_gp_box, cls) == 20, "at_gp_box");
 
 #define OFF(T, f) printf("\"%s.%s\": %zu, ", #T, #f, offsetof(T, f))
 
@@ -48,6 +49,8 @@ static int layout(void) {
   OFF(at_tag_detection, distance); OFF(at_tag_detection, err);
   OFF(at_quad_record, blob_index); OFF(at_quad_record, valid); OFF(at_quad_record, accepted);
   OFF(at_quad_record, indices); OFF(at_quad_record, corners);
+  printf("\"sizeof.at_gp_box\": %zu, ", sizeof(at_gp_box));
+  OFF(at_gp_box, x); OFF(at_gp_box, conf); OFF(at_gp_box, cls);
   printf("\"library_abi_version\": %d}\n", at_abi_version());
   return 0;
 }

@@ -440,6 +440,31 @@ void draw_detection_outlines(uint8_t* bgr, int W, int H, const at_detection* det
   }
 }
 
+void draw_boxes(uint8_t* bgr, int W, int H, const at_gp_box* boxes, int n) {
+  // (The palette, the saturating cast and the clamp are written a second time in
+  // ros_vision_amd/csrc/at_gp.h -- kGpPalette, gp_trunc, gp_box_corners -- for the device
+  // drawing: change one, change the other; tests/test_gp_parse_gpu.py compares the pixels.)
+  // detection_test.cpp:75-82, BGR
+  static const uint8_t kColors[6][3] = {{0, 255, 0}, {0, 165, 255}, {255, 0, 0}, {0, 255, 255}, {255, 0, 255}, {255, 255, 0}};
+  // static_cast<int> of a corner (:86-89; NaN -> 0, beyond int: saturated), clamped to the image (:92-95)
+  auto corner = [](float v, int hi) {
+    int i = 0;
+    if (v == v) i = v >= 2147483520.0f ? 2147483520 : (v <= -2147483520.0f ? -2147483520 : (int)v);
+    return std::max(0, std::min(i, hi));
+  };
+  for (int i = 0; i < n; ++i) {
+    const at_gp_box& b = boxes[i];
+    const int x1 = corner(b.x - b.w / 2.0f, W - 1), y1 = corner(b.y - b.h / 2.0f, H - 1);
+    const int x2 = corner(b.x + b.w / 2.0f, W - 1), y2 = corner(b.y + b.h / 2.0f, H - 1);
+    const uint8_t* c = kColors[((b.cls % 6) + 6) % 6];
+    // cv::rectangle(..., 2) as its four sides
+    thick_line(bgr, W, H, x1, y1, x2, y1, 2, c);
+    thick_line(bgr, W, H, x2, y1, x2, y2, 2, c);
+    thick_line(bgr, W, H, x2, y2, x1, y2, 2, c);
+    thick_line(bgr, W, H, x1, y2, x1, y1, 2, c);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // DetectorCore
 // ---------------------------------------------------------------------------
@@ -590,6 +615,83 @@ int DetectorCore::run(const uint8_t* frame, size_t len, int fmt, double stamp_s,
   return rc;
 }
 
+// ---------------------------------------------------------------------------
+// GamePieceCore
+// ---------------------------------------------------------------------------
+GamePieceCore::GamePieceCore(int width, int height, const GamePieceParams& params, GamePieceInfer infer,
+                             void* infer_ctx, int device)
+    : width_(width), height_(height), params_(params), infer_(infer), infer_ctx_(infer_ctx) {
+  if (!infer_) throw std::runtime_error("GamePieceCore: no infer function");
+  at_config cfg;
+  at_config_default(&cfg, width_, height_);
+  cfg.device = device;
+  cfg.tag_size = 0;  // no pose work for tags nobody reads
+  at_camera cam{};
+  cam.fx = cam.fy = 1.0;
+  int rc = at_create(&cfg, &cam, &det_);
+  if (rc != AT_OK) throw std::runtime_error(std::string("at_create: ") + at_strerror(rc));
+  rc = at_gp_enable(det_, params_.input_width, params_.input_height, params_.input_channels);
+  if (rc != AT_OK) {
+    at_destroy(det_);
+    throw std::runtime_error(std::string("at_gp_enable: ") + at_strerror(rc));
+  }
+  tags_.resize(at_max_detections());
+  boxes_.resize(AT_GP_MAX_CANDIDATES);
+}
+
+GamePieceCore::~GamePieceCore() { at_destroy(det_); }
+
+void GamePieceCore::set_image_jpeg(int quality) {
+  if (quality < 0 || quality > 100) throw std::runtime_error("set_image_jpeg: quality 1..100 (0: off)");
+  if (quality && jpeg_buf_.empty()) {
+    const size_t most = at_jpeg_max_bytes(width_, height_, AT_JPEG_420);
+    if (!most) throw std::runtime_error("set_image_jpeg: no JPEG of this frame size");
+    jpeg_buf_.resize(most);
+  }
+  image_jpeg_ = quality;
+}
+
+int GamePieceCore::process(const uint8_t* bgr, double stamp_s, GamePieceOutputs* out, ImageBuffer* annotate) {
+  *out = GamePieceOutputs{};
+  int ntags = 0;
+  // the frame into HBM and preprocess_image's tensor beside it (:283)
+  int rc = at_detect(det_, bgr, AT_FMT_BGR8, tags_.data(), (int)tags_.size(), &ntags);
+  if (rc != AT_OK && rc != AT_E_CAPACITY) return out->status = rc;
+  const float* input = nullptr;
+  if ((rc = at_gp_tensor(det_, 0, &input)) != AT_OK) return out->status = rc;
+  const float* output = nullptr;
+  void* stream = nullptr;
+  if (infer_(infer_ctx_, input, &output, &stream) != 0 || !output) return out->status = AT_E_INVALID;
+  // parse_yolov11_output + scale_detections (:287-292) where the engine left its output
+  int n = 0, status = AT_OK;
+  rc = at_gp_parse_device(det_, output, (size_t)(4 + params_.num_classes) * (size_t)params_.num_predictions, 1,
+                          params_.num_predictions, params_.num_classes, params_.conf_threshold,
+                          params_.iou_threshold, params_.input_width, params_.input_height, stream, boxes_.data(),
+                          (int)boxes_.size(), &n, &status);
+  if (rc != AT_OK) return out->status = rc;
+  out->status = status;
+  out->boxes.assign(boxes_.begin(), boxes_.begin() + n);
+  for (const at_gp_box& b : out->boxes)
+    out->class_names.push_back(b.cls >= 0 && (size_t)b.cls < params_.class_names.size() ? params_.class_names[b.cls]
+                                                                                         : "unknown");
+  if (publish_detections) publish_detections(ctx, *out, stamp_s);
+  if (annotate) {
+    if (image_jpeg_) {
+      size_t len = 0;
+      rc = at_gp_annotate_jpeg(det_, 0, out->boxes.data(), n, image_jpeg_, AT_JPEG_420, jpeg_buf_.data(),
+                               jpeg_buf_.size(), &len);
+      if (rc != AT_OK) return rc;
+      annotate->assign(jpeg_buf_.begin(), jpeg_buf_.begin() + (ptrdiff_t)len);
+    } else {
+      annotate->resize((size_t)width_ * height_ * 3);
+      rc = at_gp_annotate_staged(det_, 0, out->boxes.data(), n, annotate->data());
+      if (rc != AT_OK) return rc;
+    }
+    if (publish_image) publish_image(ctx, std::vector<uint8_t>(annotate->begin(), annotate->end()), stamp_s);
+  }
+  return status;
+}
+
 }  // namespace at_node
 
 // ---------------------------------------------------------------------------
@@ -621,6 +723,10 @@ int at_node_load_extrinsics(const char* path, const char* serial, double* R, dou
 
 void at_node_draw_detection_outlines(uint8_t* bgr, int width, int height, const at_detection* dets, int n) {
   at_node::draw_detection_outlines(bgr, width, height, dets, n);
+}
+
+void at_node_draw_boxes(uint8_t* bgr, int width, int height, const at_gp_box* boxes, int n) {
+  at_node::draw_boxes(bgr, width, height, boxes, n);
 }
 
 // ConfigLoader::getCameraConfig: width, height, frame_rate and the location string.

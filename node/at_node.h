@@ -211,6 +211,13 @@ std::string encode_apriltag_list(const at_tag_detection* tags, int n, double col
 // colours follow the reference, the exact pixels of cv::line / cv::putText do not.
 void draw_detection_outlines(uint8_t* bgr, int width, int height, const at_detection* dets, int n);
 
+// Outline every game-piece box on a bgr8 image in place (draw_detections,
+// detection_test.cpp:73-100): corners truncated to int and clamped to the image, the
+// rectangle's four sides 2 px thick in the class colour (cls % 6: green, orange, blue,
+// yellow, magenta, cyan).  The label text and its filled background are not drawn (no
+// Hershey font here).  at_gp_draw_boxes_device draws the same pixels on the GPU.
+void draw_boxes(uint8_t* bgr, int width, int height, const at_gp_box* boxes, int n);
+
 class DetectorCore {
  public:
   // width/height of the camera frames; throws std::runtime_error when at_create fails.
@@ -289,6 +296,71 @@ class DetectorCore {
   std::vector<at_pose> poses_;
   std::FILE* csv_ = nullptr;
   std::string csv_path_;
+};
+
+// ---- game-piece node (src/game_piece_detection/src/game_piece_detection_node.cu:27-332) ----
+// The user's engine.  Called with the network input of the frame, [channels][height][width]
+// floats in device memory, complete when the call is made.  It leaves the output tensor,
+// [4 + classes][P] floats, in device memory, stores its pointer in *d_output and the
+// hipStream_t the output is produced on in *stream (NULL: the null stream); it need not wait
+// for that stream.  Returns 0, or anything else to fail the frame.
+typedef int (*GamePieceInfer)(void* ctx, const float* d_input, const float** d_output, void** stream);
+
+// Parameters with the reference defaults (:34-45), the model's geometry and the thresholds
+// (CONF_THRESHOLD / IOU_THRESHOLD).
+struct GamePieceParams {
+  std::string topic_name = "camera/image_raw";
+  std::string camera_serial = "N/A";
+  std::string engine_file = "N/A";
+  std::string publish_to_topic = "game_piece_detector/images";
+  int input_width = 640, input_height = 640, input_channels = 3;
+  int num_predictions = 8400;
+  int num_classes = 1;
+  std::vector<std::string> class_names;  // class c is class_names[c], "unknown" beyond (yolo_detection.h:173-175)
+  float conf_threshold = 0.25f, iou_threshold = 0.45f;
+};
+
+struct GamePieceOutputs {
+  std::vector<at_gp_box> boxes;          // camera pixels, NMS order
+  std::vector<std::string> class_names;  // of each box
+  int status = AT_OK;                    // AT_E_CAPACITY: more than AT_GP_MAX_CANDIDATES candidates, no boxes
+};
+
+// imageCallback (:274-297) with everything between the frame's upload and the boxes' download
+// on the GPU: at_detect stages the bgr8 frame and leaves preprocess_image's tensor in HBM
+// (at_gp_enable: the staging and the launch sequence are the tag detector's, so a process that
+// runs both nodes on one camera uploads the frame once), `infer`, at_gp_parse_device, class
+// names; `annotate` (may be null) receives the frame with the boxes drawn on its staged copy
+// (at_gp_annotate_staged), or with set_image_jpeg the JPEG of that (at_gp_annotate_jpeg).
+// publish_image, if set, is called with it before process returns (no publisher queue here).
+class GamePieceCore {
+ public:
+  GamePieceCore(int width, int height, const GamePieceParams& params, GamePieceInfer infer, void* infer_ctx,
+                int device = 0);
+  ~GamePieceCore();
+  GamePieceCore(const GamePieceCore&) = delete;
+  GamePieceCore& operator=(const GamePieceCore&) = delete;
+
+  int process(const uint8_t* bgr, double stamp_s, GamePieceOutputs* out, ImageBuffer* annotate = nullptr);
+  void set_image_jpeg(int quality);  // 1..100; 0: off (the default)
+  int image_jpeg() const { return image_jpeg_; }
+  std::string compressed_image_topic() const { return params_.publish_to_topic + "/compressed"; }
+  const GamePieceParams& params() const { return params_; }
+
+  void (*publish_detections)(void* ctx, const GamePieceOutputs&, double stamp_s) = nullptr;
+  void (*publish_image)(void* ctx, const std::vector<uint8_t>&, double stamp_s) = nullptr;
+  void* ctx = nullptr;
+
+ private:
+  int width_, height_;
+  GamePieceParams params_;
+  GamePieceInfer infer_;
+  void* infer_ctx_;
+  int image_jpeg_ = 0;
+  ImageBuffer jpeg_buf_;
+  at_detector* det_ = nullptr;
+  std::vector<at_detection> tags_;  // (the staging call's tag detections: not used here)
+  std::vector<at_gp_box> boxes_;
 };
 
 }  // namespace at_node

@@ -21,6 +21,7 @@
 
 #include "../../include/at_api.h"
 #include "at_common.h"
+#include "at_gp.h"
 #include "at_mjpg.h"
 
 namespace at {
@@ -36,6 +37,8 @@ hipError_t launch_mjpg_color(const uint8_t* coef, size_t slot, const uint8_t* gr
                              hipStream_t st);
 hipError_t launch_jpg_encode(const uint8_t* bgr, int W, int H, int quality, int sampling, const JpgBufs& b,
                              hipStream_t st);
+hipError_t launch_gp_parse(const float* raw, size_t frame_stride, int nframes, int P, int C, float conf_thr,
+                           float iou_thr, float sx, float sy, const GpParseBufs& b, hipStream_t st);
 hipError_t prepare_kernels(const Geom& g);
 hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, int B, int fmt, int nblobwg,
                            hipStream_t st, hipEvent_t* ev, hipStream_t st2, hipEvent_t fork, hipEvent_t join,
@@ -229,6 +232,13 @@ struct at_detector {
   int jpg_hdr_q, jpg_hdr_s;
   uint64_t jpg_stats[2];    // last encode: bytes out, the encode kernels' ns (while profiling)
   hipEvent_t ev_jpg[2];     // around them (created on first use)
+  // game-piece output parse (at_gp_parse_device), allocated on the first call for max_batch
+  // frames and kept: candidate lists in HBM, boxes and counts in mapped page-locked memory
+  at::GpParseBufs gp;
+  at::GpBox* h_gp_out;      // [B][kGpMaxCand] the host side of gp.out
+  uint32_t* h_gp_info;      // [B][2] ... and of gp.info: boxes kept, candidates
+  uint64_t gp_stats[4];     // last call: candidates, most of one frame, boxes kept, kernel ns (while profiling)
+  hipEvent_t ev_gp[2];      // around the two kernels (created on first use)
 };
 
 // Experiment and diagnostic knobs (stage cut-offs, grid / tile overrides, phase
@@ -336,6 +346,10 @@ void at_destroy(at_detector* d) {
   for (hipEvent_t e : d->ev_jpg)
     if (e) (void)hipEventDestroy(e);
   if (d->h_jpg_total) (void)hipHostFree(d->h_jpg_total);
+  for (hipEvent_t e : d->ev_gp)
+    if (e) (void)hipEventDestroy(e);
+  if (d->h_gp_out) (void)hipHostFree(d->h_gp_out);
+  if (d->h_gp_info) (void)hipHostFree(d->h_gp_info);
   if (d->ev_done) (void)hipEventDestroy(d->ev_done);
   if (d->ev_ext) (void)hipEventDestroy(d->ev_ext);
   for (int i = 0; i <= kNumStages; i++)
@@ -1329,12 +1343,9 @@ static void outline_prims(const at_detection* dets, int n, std::vector<DrawPrim>
   }
 }
 
-// the outline segments drawn onto `bgr` on the detector's stream (not waited for)
-static int draw_outlines(at_detector* d, const at_detection* dets, int n, uint8_t* bgr) {
-  if (!d || n < 0 || (n > 0 && !dets) || !bgr) return AT_E_INVALID;
+// segments drawn onto `bgr` on the detector's stream (not waited for)
+static int draw_prims(at_detector* d, const std::vector<DrawPrim>& prims, uint8_t* bgr) {
   HIPCHK(hipSetDevice(d->device));
-  std::vector<DrawPrim> prims;
-  outline_prims(dets, n, &prims);
   if (prims.empty()) return AT_OK;
   const size_t W = (size_t)d->g.W, H = (size_t)d->g.H;
   if (!d->d_last) {
@@ -1352,6 +1363,14 @@ static int draw_outlines(at_detector* d, const at_detection* dets, int n, uint8_
   HIPCHK(hipMemcpyAsync(d->d_prims, prims.data(), prims.size() * sizeof(DrawPrim), hipMemcpyHostToDevice, d->st));
   HIPCHK(launch_draw(d->d_prims, (int)prims.size(), d->d_last, bgr, (int)W, (int)H, d->st));
   return AT_OK;
+}
+
+// the outline segments drawn onto `bgr` on the detector's stream (not waited for)
+static int draw_outlines(at_detector* d, const at_detection* dets, int n, uint8_t* bgr) {
+  if (!d || n < 0 || (n > 0 && !dets) || !bgr) return AT_E_INVALID;
+  std::vector<DrawPrim> prims;
+  outline_prims(dets, n, &prims);
+  return draw_prims(d, prims, bgr);
 }
 
 int at_draw_outlines_device(at_detector* d, const at_detection* dets, int n, uint8_t* bgr) {
@@ -1374,6 +1393,182 @@ int at_annotate_staged(at_detector* d, int frame, const at_detection* dets, int 
   // in stream order after the drawing, on the detector's stream (no null-stream copy);
   // DMA straight into a page-locked bgr_out (at_host_alloc)
   HIPCHK(hipMemcpyAsync(bgr_out, img, (size_t)d->g.W * d->g.H * 3, hipMemcpyDeviceToHost, d->st));
+  HIPCHK(hipStreamSynchronize(d->st));
+  return AT_OK;
+}
+
+// ---- game-piece output parse ------------------------------------------------------
+// k_gp_cand + k_gp_nms on the detector's stream (outside the captured graphs), behind an
+// event of the producer's stream; the kernels leave boxes and counts in mapped page-locked
+// memory, the host waits for the stream and copies them to the caller.
+static_assert(sizeof(at_gp_box) == sizeof(GpBox), "at_gp.h carries the ABI's box");
+
+static int gp_prepare(at_detector* d) {
+  if (d->gp.cnt) return AT_OK;
+  const size_t B = (size_t)d->B;
+  void *cnt = nullptr, *key = nullptr, *cls = nullptr;
+  GpBox* out = nullptr;
+  uint32_t* info = nullptr;
+  if (hipMalloc(&cnt, B * kGpCntStride * 4) != hipSuccess || hipMalloc(&key, B * kGpMaxCand * 8) != hipSuccess ||
+      hipMalloc(&cls, B * kGpMaxCand * 4) != hipSuccess ||
+      hipHostMalloc((void**)&out, B * kGpMaxCand * sizeof(GpBox), hipHostMallocMapped) != hipSuccess ||
+      hipHostMalloc((void**)&info, B * 2 * 4, hipHostMallocMapped) != hipSuccess) {
+    for (void* p : {cnt, key, cls})
+      if (p) (void)hipFree(p);
+    if (out) (void)hipHostFree(out);
+    if (info) (void)hipHostFree(info);
+    return AT_E_NOMEM;
+  }
+  for (void* p : {cnt, key, cls}) d->allocs.push_back(p);
+  d->h_gp_out = out;
+  d->h_gp_info = info;
+  memset(info, 0, B * 2 * 4);
+  HIPCHK(hipMemset(cnt, 0, B * kGpCntStride * 4));  // from here on k_gp_nms leaves every counter it read at 0
+  HIPCHK(hipHostGetDevicePointer((void**)&d->gp.out, out, 0));
+  HIPCHK(hipHostGetDevicePointer((void**)&d->gp.info, info, 0));
+  d->gp.key = (uint64_t*)key;
+  d->gp.cls = (int32_t*)cls;
+  d->gp.cnt = (uint32_t*)cnt;
+  return AT_OK;
+}
+
+static int gp_parse_run(at_detector* d, const float* d_raw, size_t frame_stride, int nframes, int num_predictions,
+                        int num_classes, float conf_thr, float iou_thr, int model_w, int model_h,
+                        void* producer_stream, at_gp_box* out, int cap_per_frame, int* n_per_frame,
+                        int* status_per_frame);
+
+int at_gp_parse_device(at_detector* d, const float* d_raw, size_t frame_stride, int nframes, int num_predictions,
+                       int num_classes, float conf_thr, float iou_thr, int model_w, int model_h,
+                       void* producer_stream, at_gp_box* out, int cap_per_frame, int* n_per_frame,
+                       int* status_per_frame) {
+  if (!d || !d_raw || !n_per_frame || cap_per_frame < 0 || (cap_per_frame > 0 && !out)) return AT_E_INVALID;
+  if (num_predictions < 1 || num_classes < 1 || nframes < 1 || nframes > d->B || !std::isfinite(conf_thr) ||
+      !std::isfinite(iou_thr) || model_w < 1 || model_h < 1)
+    return AT_E_INVALID;
+  if (frame_stride < ((size_t)num_classes + 4) * (size_t)num_predictions) return AT_E_INVALID;
+  HIPCHK(hipSetDevice(d->device));
+  const int prc = gp_prepare(d);
+  if (prc != AT_OK) return prc;
+  const int rc = gp_parse_run(d, d_raw, frame_stride, nframes, num_predictions, num_classes, conf_thr, iou_thr,
+                              model_w, model_h, producer_stream, out, cap_per_frame, n_per_frame, status_per_frame);
+  if (rc != AT_OK) {
+    // k_gp_cand may have counted without k_gp_nms zeroing after it: the next call must not start from that
+    (void)hipStreamSynchronize(d->st);
+    (void)hipMemset(d->gp.cnt, 0, (size_t)d->B * kGpCntStride * 4);
+  }
+  return rc;
+}
+
+// the launches, the wait and the copy-out of at_gp_parse_device (arguments checked, buffers there)
+static int gp_parse_run(at_detector* d, const float* d_raw, size_t frame_stride, int nframes, int num_predictions,
+                        int num_classes, float conf_thr, float iou_thr, int model_w, int model_h,
+                        void* producer_stream, at_gp_box* out, int cap_per_frame, int* n_per_frame,
+                        int* status_per_frame) {
+  HIPCHK(hipEventRecord(d->ev_ext, (hipStream_t)producer_stream));
+  HIPCHK(hipStreamWaitEvent(d->st, d->ev_ext, 0));
+  const bool timed = d->profiling != 0;
+  if (timed) {
+    for (hipEvent_t& e : d->ev_gp)
+      if (!e) HIPCHK(hipEventCreateWithFlags(&e, kTimingEventFlags));
+    HIPCHK(hipEventRecord(d->ev_gp[0], d->st));
+  }
+  HIPCHK(launch_gp_parse(d_raw, frame_stride, nframes, num_predictions, num_classes, conf_thr, iou_thr,
+                         gp_scale(d->g.W, model_w), gp_scale(d->g.H, model_h), d->gp, d->st));
+  if (timed) HIPCHK(hipEventRecord(d->ev_gp[1], d->st));
+  HIPCHK(hipStreamSynchronize(d->st));
+  uint64_t cand_sum = 0, cand_max = 0, kept_sum = 0;
+  for (int f = 0; f < nframes; f++) {
+    const volatile uint32_t* info = d->h_gp_info + 2 * f;
+    const uint32_t kept = info[0], cand = info[1];
+    if (kept > (uint32_t)kGpMaxCand) return AT_E_HIP;  // (cannot happen: at most one box per candidate)
+    cand_sum += cand;
+    cand_max = std::max<uint64_t>(cand_max, cand);
+    kept_sum += kept;
+    n_per_frame[f] = (int)kept;
+    if (status_per_frame) status_per_frame[f] = cand > (uint32_t)kGpMaxCand ? AT_E_CAPACITY : AT_OK;
+    const size_t nw = std::min<size_t>(kept, (size_t)cap_per_frame);
+    if (nw) memcpy(out + (size_t)f * cap_per_frame, d->h_gp_out + (size_t)f * kGpMaxCand, nw * sizeof(GpBox));
+  }
+  d->gp_stats[0] = cand_sum;
+  d->gp_stats[1] = cand_max;
+  d->gp_stats[2] = kept_sum;
+  d->gp_stats[3] = 0;
+  if (timed) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, d->ev_gp[0], d->ev_gp[1]));
+    d->gp_stats[3] = (uint64_t)((double)ms * 1e6);
+  }
+  return AT_OK;
+}
+
+int at_gp_parse_stats(at_detector* d, uint64_t* out, int cap) {
+  if (!d || !out || cap < 1) return AT_E_INVALID;
+  const int n = std::min(cap, 4);
+  for (int i = 0; i < n; i++) out[i] = d->gp_stats[i];
+  return n;
+}
+
+// The rectangle of detection_test.cpp:84-100 as four 2-px segments in the class colour
+// (top, right, bottom, left), as node/at_node.cpp's draw_boxes draws them.
+// (node/at_node.cpp's draw_boxes restates gp_trunc, the clamp and the palette of at_gp.h on its
+// own: change one, change the other -- tests/test_gp_parse_gpu.py compares the pixels.)
+static void box_prims(const at_detector* d, const at_gp_box* boxes, int n, std::vector<DrawPrim>* out) {
+  std::vector<DrawPrim>& prims = *out;
+  prims.reserve((size_t)n * 4);
+  for (int i = 0; i < n; i++) {
+    GpBox b;
+    memcpy(&b, boxes + i, sizeof(b));
+    int x1, y1, x2, y2;
+    gp_box_corners(b, d->g.W, d->g.H, &x1, &y1, &x2, &y2);
+    const uint8_t* c = kGpPalette[((b.cls % 6) + 6) % 6];
+    const int seg[4][4] = {{x1, y1, x2, y1}, {x2, y1, x2, y2}, {x2, y2, x1, y2}, {x1, y2, x1, y1}};
+    for (const auto& s : seg) {
+      DrawPrim q;
+      q.x0 = s[0]; q.y0 = s[1]; q.x1 = s[2]; q.y1 = s[3];
+      q.bgr[0] = c[0]; q.bgr[1] = c[1]; q.bgr[2] = c[2];
+      prims.push_back(q);
+    }
+  }
+}
+
+int at_gp_draw_boxes_device(at_detector* d, const at_gp_box* boxes, int n, uint8_t* bgr) {
+  if (!d || n < 0 || (n > 0 && !boxes) || !bgr) return AT_E_INVALID;
+  std::vector<DrawPrim> prims;
+  box_prims(d, boxes, n, &prims);
+  const int rc = draw_prims(d, prims, bgr);
+  if (rc != AT_OK) return rc;
+  HIPCHK(hipStreamSynchronize(d->st));
+  return AT_OK;
+}
+
+// the staged image of frame `frame` of the last batch, as at_annotate_staged gates it
+static int gp_staged_image(at_detector* d, int frame, uint8_t** img) {
+  if (!d->last_staged || (d->last_fmt != AT_FMT_BGR8 && !d->last_mj_color) || frame < 0 || frame >= d->last_nframes)
+    return AT_E_INVALID;
+  HIPCHK(hipSetDevice(d->device));
+  if (d->pending) HIPCHK(hipEventSynchronize(d->ev_done));
+  *img = (d->last_mj_color ? d->d_mj_bgr : d->d_in) + (size_t)frame * d->in_stride;
+  return AT_OK;
+}
+
+int at_gp_annotate_staged(at_detector* d, int frame, const at_gp_box* boxes, int n, uint8_t* bgr_out) {
+  if (!d || !bgr_out || n < 0 || (n > 0 && !boxes)) return AT_E_INVALID;
+  uint8_t* img = nullptr;
+  int rc = gp_staged_image(d, frame, &img);
+  if (rc != AT_OK) return rc;
+  std::vector<DrawPrim> prims;
+  box_prims(d, boxes, n, &prims);
+  rc = draw_prims(d, prims, img);
+  if (rc != AT_OK) return rc;
+  HIPCHK(hipMemcpyAsync(bgr_out, img, (size_t)d->g.W * d->g.H * 3, hipMemcpyDeviceToHost, d->st));
+  HIPCHK(hipStreamSynchronize(d->st));
+  return AT_OK;
+}
+
+int at_gp_copy_raw(at_detector* d, const float* d_raw, float* dst, size_t count) {
+  if (!d || !d_raw || !dst) return AT_E_INVALID;
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(hipMemcpyAsync(dst, d_raw, count * sizeof(float), hipMemcpyDeviceToHost, d->st));
   HIPCHK(hipStreamSynchronize(d->st));
   return AT_OK;
 }
@@ -1486,6 +1681,22 @@ int at_annotate_jpeg(at_detector* d, int frame, const at_detection* dets, int n,
   if (d->pending) HIPCHK(hipEventSynchronize(d->ev_done));
   uint8_t* img = (d->last_mj_color ? d->d_mj_bgr : d->d_in) + (size_t)frame * d->in_stride;
   const int rc = draw_outlines(d, dets, n, img);
+  if (rc != AT_OK) return rc;
+  return encode_jpeg(d, img, quality, sampling, out, cap, len);
+}
+
+int at_gp_annotate_jpeg(at_detector* d, int frame, const at_gp_box* boxes, int n, int quality, int sampling,
+                        uint8_t* out, size_t cap, size_t* len) {
+  if (len) *len = 0;
+  if (!d || !out || !len || n < 0 || (n > 0 && !boxes)) return AT_E_INVALID;
+  JpgGeom g;
+  if (quality < 1 || quality > 100 || !jpg_geom(d->g.W, d->g.H, sampling, &g)) return AT_E_INVALID;
+  uint8_t* img = nullptr;
+  int rc = gp_staged_image(d, frame, &img);
+  if (rc != AT_OK) return rc;
+  std::vector<DrawPrim> prims;
+  box_prims(d, boxes, n, &prims);
+  rc = draw_prims(d, prims, img);
   if (rc != AT_OK) return rc;
   return encode_jpeg(d, img, quality, sampling, out, cap, len);
 }

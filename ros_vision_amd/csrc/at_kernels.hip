@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "at_common.h"
+#include "at_gp.h"
 #include "at_mjpg.h"
 #include "at_pose.h"
 
@@ -6095,6 +6096,232 @@ hipError_t launch_jpg_encode(const uint8_t* bgr, int W, int H, int quality, int 
   hipLaunchKernelGGL(k_jpg_bits, dim3((nblk + 255) / 256), dim3(256), 0, st, b, nblk, nbr, g.bpm, nluma);
   hipLaunchKernelGGL(k_jpg_ff, dim3(g.mcuy), dim3(256), 0, st, b);
   hipLaunchKernelGGL(k_jpg_pack, dim3(g.mcuy), dim3(256), 0, st, b, g.mcuy);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Game-piece output parse (at_gp_parse_device): the network's [4 + C][P] output tensor
+// of every frame to the kept boxes, with the arithmetic of at_gp.h (shared with the CPU
+// reference at_gp_parse_host).
+//
+// k_gp_cand, grid (ceil(P / 256), frames): lane i walks the C class rows of prediction i
+// (each row read is coalesced across the wave) and keeps the first maximum above 0.
+// Survivors of the confidence threshold are compacted per workgroup (a ballot per wave,
+// the four counts summed in LDS, one atomic per workgroup on the frame's counter) as the
+// 64-bit key gp_key = (~bits(conf) << 32) | i with the class in the same slot.  Ascending
+// key order is descending confidence with ties by ascending i, whatever order the atomics
+// landed in.  The counter counts on past kGpMaxCand; slots beyond are not written.
+// (One atomic per WAVE on counters one word apart was the first version: with scattered
+// candidates nearly every one cost an atomic, all frames' on one 128-B line, and the
+// kernel took 38 us for 8 frames of P = 33600, C = 2 -- 6.4 MB -- and 30 us for 8 frames
+// of P = 8400, C = 80.  Hence one atomic per workgroup and a line per frame's counter.)
+//
+// k_gp_nms, one 1024-thread workgroup per frame: sorts the frame's keys in LDS (up to 1024
+// keys: each thread counts the keys below its own, which is its place; more: a bitonic
+// network, padded to a power of two; the compaction slot travels with the key so the class
+// can be fetched afterwards), then candidate j of the order belongs to thread j % 1024, which
+// gathers its box from the tensor into registers (4 candidates per thread: corners, area,
+// class, and x, y, w, h, conf for the output).  One 64-bit live word per 64 candidates
+// in LDS; the 64 candidates of a word are the 64 lanes of one wave, so that wave alone
+// rewrites it (one ballot, no atomics).  The greedy sweep is sequential in the KEPT boxes
+// only: all threads find the lowest live candidate p at or after the cursor (a scan of
+// the live words, the cursor never moves back), its owner publishes its corners, every
+// thread tests its own live candidates after p against it and their waves clear the
+// suppressed bits.  Two barriers per kept box (publish / clear).  The bits still set at
+// the end are the kept boxes; their rank among the set bits is their place in the output,
+// so all of them are written at once, scaled, into mapped host memory.  The kernel leaves
+// the frame's counter at 0 for the next call.  A frame with more than kGpMaxCand
+// candidates writes zero boxes and its count (the host reports AT_E_CAPACITY).
+// LDS 41 KB (keys 32, slots 8, live words, ranks, the pivot); no scratch.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_gp_cand(const float* __restrict__ raw, size_t frame_stride, int P, int C,
+                                                 float conf_thr, GpParseBufs b) {
+  const int f = blockIdx.y;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  bool cand = false;
+  float best = 0.0f;
+  int32_t cls = 0;
+  if (i < (size_t)P) {
+    gp_candidate(raw + (size_t)f * frame_stride, (size_t)P, C, i, &best, &cls);
+    cand = !gp_dropped(best, conf_thr);
+  }
+  __shared__ uint32_t s_cnt[4], s_base;
+  const uint64_t m = __ballot(cand);  // every lane of the wave is here
+  const uint32_t wave = threadIdx.x >> 6;
+  if (lane_id() == 0) s_cnt[wave] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t tot = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    s_base = tot ? atomicAdd(b.cnt + (size_t)f * kGpCntStride, tot) : 0u;
+  }
+  __syncthreads();
+  uint32_t base = s_base;
+  for (uint32_t w = 0; w < wave; w++) base += s_cnt[w];
+  const uint32_t slot = base + lanes_below(m);
+  if (cand && slot < (uint32_t)kGpMaxCand) {
+    b.key[(size_t)f * kGpMaxCand + slot] = gp_key(best, (uint32_t)i);
+    b.cls[(size_t)f * kGpMaxCand + slot] = cls;
+  }
+}
+
+constexpr int kGpNmsThreads = 1024;
+constexpr int kGpPer = kGpMaxCand / kGpNmsThreads;        // candidates per thread
+constexpr int kGpLiveWords = kGpMaxCand / 64;             // 64
+constexpr int kGpWaves = kGpNmsThreads / 64;              // 16: live word of (k, wave) is k * kGpWaves + wave
+static_assert(kGpLiveWords == 64 && kGpPer * kGpWaves == kGpLiveWords, "k_gp_nms: one live word per (k, wave)");
+
+__global__ __launch_bounds__(kGpNmsThreads) void k_gp_nms(const float* __restrict__ raw, size_t frame_stride, int P,
+                                                          float iou_thr, float sx, float sy, GpParseBufs b) {
+  __shared__ uint64_t s_key[kGpMaxCand];
+  __shared__ uint16_t s_slot[kGpMaxCand];
+  __shared__ uint64_t s_live[kGpLiveWords];
+  __shared__ uint32_t s_rank[kGpLiveWords];
+  __shared__ GpCorners s_piv;
+  __shared__ uint32_t s_n;
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const uint32_t lane = lane_id(), wave = (uint32_t)tid >> 6;
+  if (tid == 0) {
+    const uint32_t c = b.cnt[(size_t)f * kGpCntStride];
+    s_n = c;
+    b.cnt[(size_t)f * kGpCntStride] = 0;
+    b.info[2 * f + 1] = c;
+    if (c == 0 || c > (uint32_t)kGpMaxCand) b.info[2 * f] = 0;
+  }
+  __syncthreads();
+  const uint32_t ncand = s_n;
+  if (ncand == 0 || ncand > (uint32_t)kGpMaxCand) return;
+
+  // ---- order (b): sort the keys, the compaction slot beside each
+  const uint64_t* gkey = b.key + (size_t)f * kGpMaxCand;
+  uint32_t n2 = 2;
+  if (ncand <= (uint32_t)kGpNmsThreads) {
+    // a key per thread (every frame of the deployed models): its place is the number of
+    // smaller keys (they are distinct), counted over LDS broadcast reads -- two barriers
+    // instead of the bitonic network's 36 for 256 keys, 55 for 1024
+    const uint64_t mine = (uint32_t)tid < ncand ? gkey[tid] : ~0ull;
+    if ((uint32_t)tid < ncand) s_key[tid] = mine;
+    __syncthreads();
+    uint32_t rank = 0;
+    if ((uint32_t)tid < ncand) {
+#pragma unroll 8
+      for (uint32_t i = 0; i < ncand; i++) rank += s_key[i] < mine ? 1u : 0u;
+    }
+    __syncthreads();
+    if ((uint32_t)tid < ncand) {
+      s_key[rank] = mine;
+      s_slot[rank] = (uint16_t)tid;
+    }
+    __syncthreads();
+    n2 = 0;  // (sorted: the network below has nothing to do)
+  } else {
+    while (n2 < ncand) n2 <<= 1;
+    for (uint32_t j = tid; j < n2; j += kGpNmsThreads) {
+      s_key[j] = j < ncand ? gkey[j] : ~0ull;
+      s_slot[j] = (uint16_t)j;
+    }
+    __syncthreads();
+  }
+  for (uint32_t k = 2; k <= n2; k <<= 1) {
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t i = tid; i < n2; i += kGpNmsThreads) {
+        const uint32_t ixj = i ^ j;
+        if (ixj > i) {
+          const uint64_t a = s_key[i], c = s_key[ixj];
+          const bool up = (i & k) == 0;
+          if ((a > c) == up) {
+            s_key[i] = c;
+            s_key[ixj] = a;
+            const uint16_t t = s_slot[i];
+            s_slot[i] = s_slot[ixj];
+            s_slot[ixj] = t;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  // ---- gather: candidate j = tid + k * 1024 of the order into registers
+  const float* fr = raw + (size_t)f * frame_stride;
+  const int32_t* gcls = b.cls + (size_t)f * kGpMaxCand;
+  float bx[kGpPer], by[kGpPer], bw[kGpPer], bh[kGpPer], bconf[kGpPer];
+  GpCorners bc[kGpPer];
+  bool live[kGpPer];
+#pragma unroll
+  for (int k = 0; k < kGpPer; k++) {
+    const uint32_t j = (uint32_t)tid + (uint32_t)k * kGpNmsThreads;
+    live[k] = j < ncand;
+    bx[k] = by[k] = bw[k] = bh[k] = bconf[k] = 0.0f;
+    int32_t c = 0;
+    if (live[k]) {
+      const uint64_t key = s_key[j];
+      const size_t i = gp_key_index(key);
+      bconf[k] = gp_key_conf(key);
+      bx[k] = fr[i];
+      by[k] = fr[(size_t)P + i];
+      bw[k] = fr[2 * (size_t)P + i];
+      bh[k] = fr[3 * (size_t)P + i];
+      c = gcls[s_slot[j]];
+    }
+    bc[k] = gp_corners(bx[k], by[k], bw[k], bh[k], c);
+    const uint64_t m = __ballot(live[k]);
+    if (lane == 0) s_live[k * kGpWaves + wave] = m;
+  }
+
+  // ---- (c) the greedy sweep, one round per kept box
+  const uint32_t nwords = (ncand + 63) >> 6;
+  uint32_t pos = 0;
+  for (;;) {
+    __syncthreads();  // the live words are settled; the pivot of the round before has been read
+    int p = -1;
+    for (uint32_t w = pos >> 6; w < nwords; w++) {
+      uint64_t m = s_live[w];
+      if (w == (pos >> 6)) m &= ~0ull << (pos & 63);
+      if (m) {
+        p = (int)(w * 64 + (uint32_t)__builtin_ctzll(m));
+        break;
+      }
+    }
+    if (p < 0) break;  // the same p in every thread
+#pragma unroll
+    for (int k = 0; k < kGpPer; k++)
+      if ((uint32_t)p == (uint32_t)tid + (uint32_t)k * kGpNmsThreads) s_piv = bc[k];
+    __syncthreads();
+    const GpCorners a = s_piv;
+#pragma unroll
+    for (int k = 0; k < kGpPer; k++) {
+      const uint32_t j = (uint32_t)tid + (uint32_t)k * kGpNmsThreads;
+      const bool sup = live[k] && j > (uint32_t)p && gp_suppresses(a, bc[k], iou_thr);
+      const uint64_t m = __ballot(sup);
+      if (m && lane == 0) s_live[k * kGpWaves + wave] &= ~m;
+      if (sup) live[k] = false;
+    }
+    pos = (uint32_t)p + 1;
+  }
+
+  // ---- (d) the set bits are the kept boxes, in order: rank = place in the output
+  if (wave == 0) {
+    const uint32_t c = lane < nwords ? (uint32_t)__popcll(s_live[lane]) : 0u;
+    const uint32_t incl = wave_incl_scan(c, AddOp(), 0u);
+    s_rank[lane] = incl - c;
+    if (lane == 63) b.info[2 * f] = incl;
+  }
+  __syncthreads();
+  GpBox* out = b.out + (size_t)f * kGpMaxCand;
+#pragma unroll
+  for (int k = 0; k < kGpPer; k++) {
+    if (!live[k]) continue;
+    const uint32_t w = k * kGpWaves + wave;
+    const uint32_t r = s_rank[w] + (uint32_t)__popcll(s_live[w] & ((1ull << lane) - 1));
+    out[r] = gp_scaled(bx[k], by[k], bw[k], bh[k], bconf[k], bc[k].cls, sx, sy);
+  }
+}
+
+hipError_t launch_gp_parse(const float* raw, size_t frame_stride, int nframes, int P, int C, float conf_thr,
+                           float iou_thr, float sx, float sy, const GpParseBufs& b, hipStream_t st) {
+  hipLaunchKernelGGL(k_gp_cand, dim3(((unsigned)P + 255u) / 256u, nframes), dim3(256), 0, st, raw, frame_stride, P, C,
+                     conf_thr, b);
+  hipLaunchKernelGGL(k_gp_nms, dim3(nframes), dim3(kGpNmsThreads), 0, st, raw, frame_stride, P, iou_thr, sx, sy, b);
   return hipGetLastError();
 }
 

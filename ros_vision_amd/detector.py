@@ -39,7 +39,12 @@ EXPORTS = [
     "at_mjpg_decode_gray_host", "at_mjpg_stream_mode_host",
     "at_mjpg_set_color", "at_mjpg_bgr", "at_mjpg_copy_bgr", "at_mjpg_decode_bgr_host",
     "at_encode_jpeg_device", "at_annotate_jpeg", "at_jpeg_max_bytes", "at_jpeg_stats", "at_jpeg_encode_host",
+    "at_gp_parse_host", "at_gp_parse_device", "at_gp_draw_boxes_device", "at_gp_parse_stats",
+    "at_gp_annotate_staged", "at_gp_annotate_jpeg", "at_gp_copy_raw",
 ]
+AT_GP_MAX_CANDIDATES = 4096
+# at_gp_box as a numpy record (the bit-exact view of what the library wrote)
+GP_BOX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("conf", "<f4"), ("cls", "<i4")])
 JPEG_SAMPLINGS = {"4:2:0": 0, "4:2:2": 1, "4:4:4": 2}  # AT_JPEG_420 / 422 / 444
 
 TAG_SIZE = 0.1651  # metres, apriltags_cuda_detector.hpp:39
@@ -232,6 +237,18 @@ def load_library(path: str = LIB_PATH):
         L.at_host_free.restype = None
         L.at_jpeg_encode_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                           C.POINTER(C.c_size_t)]
+    if hasattr(L, "at_gp_parse_host"):  # (A/B builds of older sources lack the output parse)
+        L.at_gp_parse_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.at_gp_parse_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_float,
+                                         C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.at_gp_draw_boxes_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.at_gp_parse_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.at_gp_annotate_staged.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.at_gp_annotate_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_size_t, C.POINTER(C.c_size_t)]
+        L.at_gp_copy_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     _LIB = L
     return L
 
@@ -338,6 +355,69 @@ def game_piece_preprocess_device(bgr_ptr: int, width: int, height: int, out_ptr:
     into a device NCHW float buffer, enqueued on `stream` (hipStream_t handle)."""
     _check(load_library().at_gp_preprocess_device(bgr_ptr, width, height, out_ptr, out_width, out_height, channels,
                                                   stream or None), "at_gp_preprocess_device")
+
+
+@dataclass
+class GamePieceBox:
+    """YoloDetection (yolo_detection.h:13-48) after scale_detections: centre, size in camera
+    pixels, confidence, class (and its name where the node knows the model's class names)."""
+    x: float
+    y: float
+    w: float
+    h: float
+    conf: float
+    cls: int
+    class_name: str = ""
+
+
+class GamePieceCapacityError(RuntimeError):
+    """game_piece_parse: `frame` had more than AT_GP_MAX_CANDIDATES candidates."""
+
+    def __init__(self, frame):
+        super().__init__("at_gp_parse_device: frame %d exceeded %d candidates (AT_E_CAPACITY)"
+                         % (frame, AT_GP_MAX_CANDIDATES))
+        self.frame, self.code = frame, AT_E_CAPACITY
+
+
+def game_piece_boxes(records, class_names=()):
+    """GP_BOX_DTYPE records -> [GamePieceBox]."""
+    names = list(class_names)
+    return [GamePieceBox(float(r["x"]), float(r["y"]), float(r["w"]), float(r["h"]), float(r["conf"]), int(r["cls"]),
+                         names[int(r["cls"])] if 0 <= int(r["cls"]) < len(names) else ("unknown" if names else ""))
+            for r in records]
+
+
+def _gp_parse_host_frame(raw, conf, iou, model_size, orig_size, cap=None):
+    L = load_library()
+    c4, p = raw.shape
+    n = C.c_int()
+    args = (raw.ctypes.data, p, c4 - 4, conf, iou, int(model_size[0]), int(model_size[1]), int(orig_size[0]),
+            int(orig_size[1]))
+    if cap is None:
+        _check(L.at_gp_parse_host(*args, None, 0, C.byref(n)), "at_gp_parse_host")
+        cap = n.value
+    out = np.zeros(max(int(cap), 1), GP_BOX_DTYPE)
+    _check(L.at_gp_parse_host(*args, out.ctypes.data, int(cap), C.byref(n)), "at_gp_parse_host")
+    return out[:min(n.value, int(cap))], n.value
+
+
+def game_piece_parse_host(raw, conf=0.25, iou=0.45, model_size=(640, 640), orig_size=None, records=False):
+    """at_gp_parse_host: the reference node's parse_yolov11_output + apply_nms +
+    scale_detections of a network output `raw`, [4 + C, P] or [B, 4 + C, P] float32, on the
+    host (no device needed) -- the CPU reference of GpuDetector.game_piece_parse.
+    model_size / orig_size are (width, height); orig_size None leaves model coordinates.
+    Returns the boxes in NMS order ([GamePieceBox], or GP_BOX_DTYPE records with
+    records=True); one list per frame for a 3-D `raw`."""
+    raw = np.ascontiguousarray(raw, np.float32)
+    orig_size = model_size if orig_size is None else orig_size
+    if raw.ndim not in (2, 3) or raw.shape[-2] < 5 or raw.shape[-1] < 1:
+        raise RuntimeError("at_gp_parse_host failed: raw must be [4 + C, P] or [B, 4 + C, P] (%d)" % AT_E_INVALID)
+    frames = raw[None] if raw.ndim == 2 else raw
+    res = []
+    for fr in frames:
+        rec, _ = _gp_parse_host_frame(fr, conf, iou, model_size, orig_size)
+        res.append(rec if records else game_piece_boxes(rec))
+    return res[0] if raw.ndim == 2 else res
 
 
 def family_entries(family: str = "tag36h11"):
@@ -754,6 +834,87 @@ class GpuDetector:
         out = np.empty(self._gp, np.float32)
         _check(load_library().at_gp_copy(self._h, frame, out.ctypes.data, out.size), "at_gp_copy")
         return out
+
+    # ---- game-piece output parse (yolo_detection.h:53-209) -------------------------
+    def game_piece_parse(self, raw, conf=0.25, iou=0.45, model_size=(640, 640), producer_stream=None, strict=True,
+                         records=False, cap=None):
+        """at_gp_parse_device: the network's output tensors, resident in device memory, to the
+        boxes in camera pixels (this detector's width x height) -- confidence threshold,
+        per-class greedy NMS and scaling on the GPU; only the boxes cross the link.
+
+        `raw` is a CUDA torch tensor [4 + C, P] or [B, 4 + C, P] (float32, each frame
+        contiguous), or (ptr, nframes, C, P[, frame_stride in floats]).  The parse is ordered
+        after the work queued so far on `producer_stream` (a torch stream or a hipStream_t
+        handle; None: the null stream), with no host wait in between.  Returns one list of
+        boxes per frame, NMS order ([GamePieceBox], or GP_BOX_DTYPE records with
+        records=True; at most `cap` per frame, default all).  A frame with more than
+        AT_GP_MAX_CANDIDATES candidates raises GamePieceCapacityError naming it; with
+        strict=False that frame is instead computed by game_piece_parse_host from a copy of
+        its tensor."""
+        L = load_library()
+        tensor = None
+        if isinstance(raw, (tuple, list)):
+            ptr, nframes, nc, p = (int(v) for v in raw[:4])
+            stride = int(raw[4]) if len(raw) > 4 else (4 + nc) * p
+        else:
+            tensor = raw if raw.dim() == 3 else raw[None]
+            if not tensor.is_cuda or str(tensor.dtype) != "torch.float32" or tensor.dim() != 3:
+                raise RuntimeError("game_piece_parse: raw must be a float32 CUDA tensor [B, 4 + C, P]")
+            if tensor.stride(2) != 1 or tensor.stride(1) != tensor.shape[2]:
+                tensor = tensor.contiguous()
+            nframes, nc, p = tensor.shape[0], tensor.shape[1] - 4, tensor.shape[2]
+            stride = tensor.stride(0) if nframes > 1 else (4 + nc) * p
+            ptr = tensor.data_ptr()
+        if hasattr(producer_stream, "cuda_stream"):
+            producer_stream = producer_stream.cuda_stream
+        limit = None if cap is None else int(cap)       # (the host route has no candidate cap of its own)
+        cap = AT_GP_MAX_CANDIDATES if cap is None else int(cap)
+        nf = max(int(nframes), 1)
+        out = np.zeros((nf, max(cap, 1)), GP_BOX_DTYPE)
+        n, status = (C.c_int * nf)(), (C.c_int * nf)()
+        _check(L.at_gp_parse_device(self._h, C.c_void_p(ptr), stride, nframes, p, nc, conf, iou, int(model_size[0]),
+                                    int(model_size[1]), C.c_void_p(producer_stream or 0), out.ctypes.data, cap, n,
+                                    status), "at_gp_parse_device")
+        res = []
+        for f in range(nframes):
+            if status[f] == AT_E_CAPACITY:
+                if strict:
+                    raise GamePieceCapacityError(f)
+                host = (tensor[f].cpu().numpy() if tensor is not None
+                        else self._copy_raw(ptr + 4 * stride * f, (4 + nc, p)))
+                rec, _ = _gp_parse_host_frame(np.ascontiguousarray(host, np.float32), conf, iou, model_size,
+                                              (self.width, self.height))
+                rec = rec[:limit]
+            else:
+                _check(status[f], "at_gp_parse_device (frame %d)" % f)
+                rec = out[f, :min(n[f], cap)].copy()
+            res.append(rec if records else game_piece_boxes(rec))
+        return res
+
+    def _copy_raw(self, ptr, shape):
+        """at_gp_copy_raw: a float32 array copied out of device memory on the detector's stream."""
+        out = np.empty(shape, np.float32)
+        _check(load_library().at_gp_copy_raw(self._h, C.c_void_p(ptr), out.ctypes.data, out.size), "at_gp_copy_raw")
+        return out
+
+    def game_piece_draw_boxes_device(self, bgr_ptr: int, boxes):
+        """at_gp_draw_boxes_device: the boxes' outlines (2 px, class colour) drawn onto the
+        device-resident BGR8 image at `bgr_ptr` (width x height x 3).  `boxes`: GamePieceBox
+        objects or GP_BOX_DTYPE records."""
+        if isinstance(boxes, np.ndarray) and boxes.dtype == GP_BOX_DTYPE:
+            rec = np.ascontiguousarray(boxes)
+        else:
+            rec = np.array([(b.x, b.y, b.w, b.h, b.conf, b.cls) for b in boxes], GP_BOX_DTYPE)
+        _check(load_library().at_gp_draw_boxes_device(self._h, rec.ctypes.data if len(rec) else None, len(rec),
+                                                      C.c_void_p(bgr_ptr)), "at_gp_draw_boxes_device")
+
+    GP_PARSE_STATS = ("candidates", "max_candidates_per_frame", "boxes", "kernels_ns")
+
+    def game_piece_parse_stats(self):
+        """at_gp_parse_stats of the last game_piece_parse."""
+        buf = (C.c_uint64 * len(self.GP_PARSE_STATS))()
+        n = _check(load_library().at_gp_parse_stats(self._h, buf, len(buf)), "at_gp_parse_stats")
+        return dict(zip(self.GP_PARSE_STATS, [int(x) for x in buf[:n]]))
 
     # ---- parity taps (apriltag_gpu.h:98-183) -------------------------------
     def _copy(self, stage, frame, nbytes, dtype):

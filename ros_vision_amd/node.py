@@ -111,6 +111,102 @@ def draw_detection_outlines(bgr, dets):
     return bgr
 
 
+GAME_PIECE_PARAMETER_DEFAULTS = {   # game_piece_detection_node.cu:34-45
+    "topic_name": "camera/image_raw",
+    "camera_serial": "N/A",
+    "engine_file": "N/A",
+    "publish_to_topic": "game_piece_detector/images",
+}
+
+
+@dataclass
+class GamePieceResult:
+    """What one GamePieceDetector::imageCallback produces: the scaled detections, and the
+    frame with their boxes (the reference node's image publisher, :301-307)."""
+    boxes: list = field(default_factory=list)     # [GamePieceBox], class_name filled in
+    image: np.ndarray = None
+    image_jpeg: bytes = None
+
+
+class GamePieceDetectorNode:
+    """GamePieceDetector (game_piece_detection_node.cu:27-332) without the ROS transport,
+    everything between the frame's upload and the boxes' download on the GPU:
+
+    bgr8 frame -> HBM -> preprocess_image (at_gp_preprocess_device) -> `infer` -> output
+    parse (at_gp_parse_device: threshold, NMS, scaling) -> boxes with class names; with an
+    image topic bound (publishers[publish_to_topic], or its "/compressed" with image_jpeg)
+    the boxes are drawn on the frame in HBM (at_gp_draw_boxes_device) and the image is
+    copied out raw or JPEG-encoded there (at_encode_jpeg_device).
+
+    `infer` is the user's engine: it gets the network input, a float32 CUDA torch tensor
+    [1, C, H, W] on the current torch stream, and returns the output [1, 4 + classes, P]
+    as a float32 CUDA tensor (produced on that stream).  input = (width, height,
+    channels) of the model."""
+
+    def __init__(self, width, height, infer, input=(640, 640, 3), class_names=(), conf=0.25, iou=0.45,  # noqa: A002
+                 image_jpeg=None, parameters=None, publishers=None, device=0):
+        import torch
+        self._torch = torch
+        self.params = dict(GAME_PIECE_PARAMETER_DEFAULTS)
+        self.params.update(parameters or {})
+        self.width, self.height = int(width), int(height)
+        self.infer = infer
+        self.input_width, self.input_height, self.input_channels = (int(v) for v in input)
+        self.class_names = list(class_names)
+        self.conf, self.iou = float(conf), float(iou)
+        self.image_jpeg = None if image_jpeg is None else int(image_jpeg)
+        if self.image_jpeg is not None and not 1 <= self.image_jpeg <= 100:
+            raise ValueError("image_jpeg is a JPEG quality, 1..100")
+        self.publishers = publishers or {}
+        self.image_topic = self.params["publish_to_topic"]
+        self.compressed_image_topic = self.image_topic + "/compressed"
+        self.detections_topic = self.image_topic.rsplit("/", 1)[0] + "/detections"
+        self.device = torch.device("cuda", int(device))
+        self.detector = GpuDetector(self.width, self.height, device=device, tag_size=0.0)
+        self._frame = torch.empty((self.height, self.width, 3), dtype=torch.uint8, device=self.device)
+        self._tensor = torch.empty((1, self.input_channels, self.input_height, self.input_width),
+                                   dtype=torch.float32, device=self.device)
+
+    def close(self):
+        self.detector.close()
+
+    def _publish(self, topic, payload):
+        fn = self.publishers.get(topic)
+        if fn is not None:
+            fn(payload)
+
+    def image_callback(self, image, stamp_s=0.0):
+        """One bgr8 frame [H, W, 3] (cv_bridge::toCvCopy(msg, "bgr8"), :275)."""
+        from .detector import game_piece_boxes, game_piece_preprocess_device
+        torch = self._torch
+        image = np.ascontiguousarray(image, np.uint8)
+        if image.shape != (self.height, self.width, 3):
+            raise ValueError("frame is %s, the node takes %s" % (image.shape, (self.height, self.width, 3)))
+        stream = torch.cuda.current_stream(self.device)
+        self._frame.copy_(torch.from_numpy(image), non_blocking=False)
+        game_piece_preprocess_device(self._frame.data_ptr(), self.width, self.height, self._tensor.data_ptr(),
+                                     self.input_width, self.input_height, self.input_channels, stream.cuda_stream)
+        raw = self.infer(self._tensor)
+        rec = self.detector.game_piece_parse(raw, self.conf, self.iou, (self.input_width, self.input_height),
+                                             producer_stream=stream, records=True)[0]
+        res = GamePieceResult(boxes=game_piece_boxes(rec, self.class_names or ()))
+        want_raw, want_jpeg = self.image_topic in self.publishers, self.compressed_image_topic in self.publishers
+        if (self.image_jpeg is None and want_raw) or (self.image_jpeg is not None and want_jpeg):
+            # (the parse waited for `stream`: the preprocessing is done with the frame it now draws on)
+            self.detector.game_piece_draw_boxes_device(self._frame.data_ptr(), rec)
+            if self.image_jpeg is not None:
+                res.image_jpeg = self.detector.encode_jpeg_device(self._frame.data_ptr(), quality=self.image_jpeg,
+                                                                  sampling="4:2:0")
+            else:
+                res.image = self._frame.cpu().numpy()
+        self._publish(self.detections_topic, res.boxes)
+        if res.image is not None:
+            self._publish(self.image_topic, res.image)
+        if res.image_jpeg is not None:
+            self._publish(self.compressed_image_topic, res.image_jpeg)
+        return res
+
+
 @dataclass
 class FrameResult:
     """Everything one imageCallback publishes."""
