@@ -184,6 +184,45 @@ int at_mjpg_decode_gray_host(const uint8_t *jpg, size_t len, uint8_t *gray, size
 int at_mjpg_decode_bgr_host(const uint8_t *jpg, size_t len, uint8_t *bgr, size_t cap, int *w, int *h);
 int at_mjpg_stream_mode_host(const uint8_t *jpg, size_t len, int want_w, int want_h, size_t *stream_bytes);
 
+/* Entropy decode on the GPU (off by default; takes effect from the next at_enqueue_mjpg).
+ * With it on, at_enqueue_mjpg only parses each frame's markers on the host (SOI .. SOS, the
+ * quantisation and Huffman tables, Annex K defaults included, the size and sampling checks:
+ * the structural refusals, *bad_frame and "nothing enqueued" are exactly those above) and
+ * sends the frame as it is: the stream headers, a table block (the decode tables the scan
+ * names and its geometry, at most 9.4 KB) and the raw scan bytes, stuffing and RSTn markers
+ * still in.  k_mjpg_entropy then decodes the scan in parallel -- each thread a piece of S
+ * bytes, the threads exchanging entry states until nothing changes, which is within
+ * `pieces` rounds and gives the serial decode exactly -- and leaves the dense coefficient
+ * layout k_mjpg_idct and the colour kernels read; nothing returns to the host in between.
+ * Colour (at_mjpg_set_color) works as with the switch off.
+ *   A frame whose scan data exceeds width * height bytes takes the host route inside the
+ * same batch (decoded and packed by the host as with the switch off): no frame fails for
+ * size.
+ *   Errors in the entropy-coded data (a code no table has, a run past coefficient 63, bits
+ * needed from beyond the data, a wrong or missing RSTn, too few blocks) are only seen on
+ * the device.  at_enqueue_mjpg succeeds; all coefficients of such a frame are left zero, so
+ * its plane is a flat 128 and it has no detections; at_frame_status gives AT_E_INVALID for
+ * it and at_collect returns AT_E_INVALID (in front of AT_E_CAPACITY) while the other
+ * frames' results stay valid.  The streams accepted are exactly those the host decoder
+ * accepts.
+ *   at_mjpg_stats gains [6] the time of k_mjpg_entropy in nanoseconds (measured like [4]),
+ * [7] frames that took the host route, [8] the most synchronisation rounds a frame of the
+ * batch needed (known once the batch is collected); with the switch on [1] counts the bytes
+ * that crossed the link.  Callers passing cap 6 see no change.
+ *   at_mjpg_set_subseq sets S (a power of two from 16 to 256 bytes, default 128; a tuning
+ * aid, AT_E_INVALID otherwise). */
+int at_mjpg_set_device_entropy(at_detector *d, int enable);
+int at_mjpg_set_subseq(at_detector *d, int bytes);
+/* Host only: the same parallel algorithm run sequentially over the pieces -- the CPU
+ * reference of k_mjpg_entropy.  Writes the frame's dense coefficient streams (headers and
+ * payloads; with keep_chroma the Cb / Cr sub-streams) to out; *rounds (may be NULL) is the
+ * number of synchronisation rounds.  at_mjpg_dense_host writes what the serial host decoder
+ * gives in the same layout (out == NULL: only *out_bytes, the size of either). */
+int at_mjpg_entropy_host(const uint8_t *jpg, size_t len, int want_w, int want_h, int subseq_bytes, int keep_chroma,
+                         uint8_t *out, size_t cap, int *rounds);
+int at_mjpg_dense_host(const uint8_t *jpg, size_t len, int want_w, int want_h, int keep_chroma, uint8_t *out,
+                       size_t cap, size_t *out_bytes);
+
 /* Stream ordering without a host wait: the detector's next enqueued batch starts
  * only after everything queued so far on `stream` (a hipStream_t of the same
  * device, e.g. the stream a frame scatter or copy was issued on; NULL = the null
@@ -192,7 +231,9 @@ int at_mjpg_stream_mode_host(const uint8_t *jpg, size_t len, int want_w, int wan
 int at_stream_wait(at_detector *d, void *stream);
 
 /* Per-frame status of the last batch: 0 or AT_E_CAPACITY (a frame whose blob
- * pair count exceeded the reference's 12-bit blob index, points.h:183-193). */
+ * pair count exceeded the reference's 12-bit blob index, points.h:183-193); after an MJPG
+ * batch with the device entropy decode on, AT_E_INVALID for a frame whose entropy-coded
+ * data was bad (at_mjpg_set_device_entropy). */
 int at_frame_status(at_detector *d, int frame);
 
 /* Per-stage parity taps (the reference's Copy*To debug accessors,

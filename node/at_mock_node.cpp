@@ -15,7 +15,7 @@
 // usage: at_mock_node --camera-serial S --format bgr8|yuyv|gray|mjpg --frames F [--count N]
 //        [--vision-config-dir D] [--pin-to-core C --priority P]
 //        [--measurement-csv PATH] [--proto-out P] [--image-out I] [--device K] [--time N]
-//        [--mjpg-color] [--jpeg-out DIR] [--jpeg-quality Q]
+//        [--mjpg-color] [--mjpg-device-entropy] [--jpeg-out DIR] [--jpeg-quality Q]
 //   As the reference node (apriltags_cuda_detector.cu:137-193): the frame size, the
 //   intrinsics and the extrinsics come from the camera serial's records in the
 //   vision_config_data share directory, found through $AMENT_PREFIX_PATH
@@ -89,11 +89,11 @@ int main(int argc, char** argv) {
   int W = 0, H = 0, count = -1, device = 0, pin = -1, priority = 80, time_n = 0, jpeg_quality = 95;
   std::string fmt_s = "yuyv", frames_path, calib_dir, serial = "N/A", sys_cfg, csv, proto_out, image_out, share_dir;
   std::string jpeg_out;
-  bool mjpg_color = false;
+  bool mjpg_color = false, mjpg_device_entropy = false;
   for (int i = 1; i < argc; i += 2) {
     const std::string k = argv[i];
-    if (k == "--mjpg-color") {  // (the one option without a value)
-      mjpg_color = true;
+    if (k == "--mjpg-color" || k == "--mjpg-device-entropy") {  // (the options without a value)
+      (k == "--mjpg-color" ? mjpg_color : mjpg_device_entropy) = true;
       i -= 1;
       continue;
     }
@@ -184,6 +184,7 @@ int main(int argc, char** argv) {
     core.publish_camera = on_camera;
     core.ctx = &sink;
     if (mjpg && mjpg_color) core.set_mjpg_color(true);
+    if (mjpg && mjpg_device_entropy) core.set_mjpg_device_entropy(true);
     if (!jpeg_out.empty()) {
       core.set_image_jpeg(jpeg_quality);
       ::mkdir(jpeg_out.c_str(), 0777);  // (exists already: fine)

@@ -532,6 +532,11 @@ void DetectorCore::set_mjpg_color(bool on) {
   mjpg_color_ = on;
 }
 
+void DetectorCore::set_mjpg_device_entropy(bool on) {
+  const int rc = at_mjpg_set_device_entropy(det_, on ? 1 : 0);
+  if (rc != AT_OK) throw std::runtime_error(std::string("at_mjpg_set_device_entropy: ") + at_strerror(rc));
+}
+
 void DetectorCore::set_image_jpeg(int quality) {
   if (quality < 0 || quality > 100) throw std::runtime_error("set_image_jpeg: quality 1..100 (0: off)");
   if (quality && jpeg_buf_.empty()) {

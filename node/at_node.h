@@ -247,6 +247,11 @@ class DetectorCore {
   int process_compressed(const uint8_t* data, size_t len, double stamp_s, double receive_s, FrameOutputs* out,
                          ImageBuffer* annotate = nullptr);
   void set_mjpg_color(bool on);
+  // set_mjpg_device_entropy(true): the GPU also decodes the frame's entropy-coded data
+  // (at_mjpg_set_device_entropy); the host only parses the markers.  A frame whose data turns
+  // out bad there comes back as AT_E_INVALID from process_compressed like one the host
+  // refuses, and nothing is published for it.
+  void set_mjpg_device_entropy(bool on);
   // set_image_jpeg(quality), 1..100 (0: off, the default): the annotated image is also
   // JPEG-encoded on the GPU (at_annotate_jpeg, 4:2:0 as cv::imencode writes) and only the
   // compressed bytes cross the link.  `annotate` then receives the JPEG file instead of the

@@ -42,6 +42,7 @@ class ApriltagsAmdNode : public rclcpp::Node {
     p.measurement_mode = declare_parameter<bool>("measurement_mode", p.measurement_mode);
     p.timing_csv_path = declare_parameter<std::string>("timing_csv_path", p.timing_csv_path);
     const int image_jpeg = declare_parameter<int>("image_jpeg", 0);
+    const bool mjpg_device_entropy = declare_parameter<bool>("mjpg_device_entropy", false);
     // optional override of the share directory (not passed by the launch file)
     std::string share_dir = declare_parameter<std::string>("vision_config_dir", "");
     if (share_dir.empty()) {
@@ -71,6 +72,7 @@ class ApriltagsAmdNode : public rclcpp::Node {
       static_cast<ApriltagsAmdNode*>(c)->camera_pose_pub_->publish(to_msg(v));
     };
     if (image_jpeg) core_->set_image_jpeg(image_jpeg);
+    if (mjpg_device_entropy) core_->set_mjpg_device_entropy(true);  // compressed frames: entropy decode on the GPU
     core_->publish_image = [](void* c, const std::vector<uint8_t>& bgr, double stamp_s) {
       auto* self = static_cast<ApriltagsAmdNode*>(c);  // publisher-queue thread
       if (self->core_->image_jpeg()) {  // the payload is the JPEG file

@@ -23,6 +23,7 @@
 #include "at_common.h"
 #include "at_gp.h"
 #include "at_mjpg.h"
+#include "at_mjpg_entropy.h"
 
 namespace at {
 hipError_t launch_tap_sizes(const uint8_t* thr, const uint32_t* par, const uint32_t* size, uint32_t* out, int Wd,
@@ -35,6 +36,7 @@ hipError_t launch_mjpg_idct(const uint8_t* coef, size_t slot, uint8_t* out, size
 hipError_t launch_mjpg_color(const uint8_t* coef, size_t slot, const uint8_t* gray, uint8_t* planes,
                              size_t plane_stride, uint8_t* bgr, size_t img_stride, int W, int H, int nframes,
                              hipStream_t st);
+hipError_t launch_mjpg_entropy(const EntBufs& b, int nframes, hipStream_t st);
 hipError_t launch_jpg_encode(const uint8_t* bgr, int W, int H, int quality, int sampling, const JpgBufs& b,
                              hipStream_t st);
 hipError_t launch_gp_parse(const float* raw, size_t frame_stride, int nframes, int P, int C, float conf_thr,
@@ -210,8 +212,8 @@ struct at_detector {
   std::vector<int> mj_rc;
   std::vector<size_t> mj_bytes;   // per frame: bytes of its coefficient stream
   std::vector<uint8_t> mj_dense;  // ... and whether it took the dense encoding
-  uint64_t mj_stats[6];     // last MJPG batch: compressed bytes, bytes sent, dense frames, decode us, kernel ns,
-                            // colour kernels ns
+  uint64_t mj_stats[9];     // last MJPG batch: compressed bytes, bytes sent, dense frames, decode us, kernel ns,
+                            // colour kernels ns, entropy kernel ns, host-route frames, most sync rounds
   hipEvent_t ev_mj[3];      // around k_mjpg_idct, and after the colour kernels, while stage profiling is on
                             // (created on first use)
   int mj_timed;             // the pending batch recorded them (2: the colour one too)
@@ -222,6 +224,19 @@ struct at_detector {
   uint8_t* d_mj_planes;     // [B][2][mj_plane]
   size_t mj_plane;
   uint8_t* d_mj_bgr;        // [B][in_stride]
+  // entropy decode on the device (at_mjpg_set_device_entropy), allocated on the first MJPG call
+  // with the switch on: the batch as it crosses the link (a directory, then per frame its record
+  // and scan bytes; two page-locked staging sets used in turn like mj_host) and k_mjpg_entropy's
+  // scratch
+  int mj_dev_ent;           // the setting; takes effect at the next at_enqueue_mjpg
+  int mj_subseq;            // piece size S in bytes
+  uint8_t* mj_ent_host[2];
+  size_t mj_ent_cap;        // bytes of one set, and of the device copy
+  at::EntBufs ent;          // (ent.in: the device copy)
+  uint32_t* h_ent_info;     // page-locked copy of ent.info
+  int mj_ent_batch;         // the pending / last batch went through k_mjpg_entropy (h_ent_info is its status)
+  hipEvent_t ev_ent[2];     // around k_mjpg_entropy while stage profiling is on (created on first use)
+  int mj_ent_timed;
   // JPEG output (at_encode_jpeg_device), allocated on the first call at the worst case of
   // this geometry (4:4:4, every block at its longest, every byte stuffed) and kept
   at::JpgBufs jpg;
@@ -343,6 +358,11 @@ void at_destroy(at_detector* d) {
     if (p) (void)hipHostFree(p);
   for (hipEvent_t e : d->ev_mj)
     if (e) (void)hipEventDestroy(e);
+  for (uint8_t* p : d->mj_ent_host)
+    if (p) (void)hipHostFree(p);
+  if (d->h_ent_info) (void)hipHostFree(d->h_ent_info);
+  for (hipEvent_t e : d->ev_ent)
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : d->ev_jpg)
     if (e) (void)hipEventDestroy(e);
   if (d->h_jpg_total) (void)hipHostFree(d->h_jpg_total);
@@ -383,6 +403,7 @@ int at_create(const at_config* cfg, const at_camera* cam, at_detector** out) {
   d->device = cfg->device;
   d->B = cfg->max_batch;
   d->mj_threads = 1;
+  d->mj_subseq = at::kEntSubseqDefault;
   Geom& g = d->g;
   g.W = W; g.H = H; g.Wd = W / 2; g.Hd = H / 2;
   g.TW = g.Wd / 4; g.TH = g.Hd / 4;
@@ -801,6 +822,7 @@ static int enqueue(at_detector* d, int nframes, int fmt) {
   d->last_sizes = d->g.ctw == 32 || d->prm.taps;     // (throughput mode: the size plane for the taps only)
   d->last_gp = d->prm.gp_c && fmt == AT_FMT_BGR8;
   d->last_mj_color = 0;  // (at_enqueue_mjpg sets it after a colour-on batch)
+  d->mj_ent_batch = 0;   // (... and this after a batch decoded by k_mjpg_entropy)
   d->pending = 1;
   return AT_OK;
 }
@@ -834,6 +856,17 @@ static int collect(at_detector* d, at_detection* out, int cap_per_frame, int* n_
     }
     d->mj_timed = 0;
   }
+  if (d->mj_ent_timed) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, d->ev_ent[0], d->ev_ent[1]));
+    d->mj_stats[6] = (uint64_t)((double)ms * 1e6);
+    d->mj_ent_timed = 0;
+  }
+  if (d->mj_ent_batch) {
+    uint32_t most = 0;
+    for (int f = 0; f < d->last_nframes; f++) most = std::max(most, d->h_ent_info[(size_t)f * at::kEntInfoWords + 1]);
+    d->mj_stats[8] = most;
+  }
   if (d->kt.stage >= 0) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, d->kt.t0, d->kt.t1));
@@ -849,6 +882,7 @@ static int collect(at_detector* d, at_detection* out, int cap_per_frame, int* n_
   }
   const int B = d->B;
   int rc = AT_OK;
+  bool bad_entropy = false;
   // each frame's candidates: its slots 0 .. ndets[f] (the first kDetPoolPerFrame
   // already in the host mirror; a frame with more is copied from HBM)
   const int nf = d->last_nframes;
@@ -864,7 +898,9 @@ static int collect(at_detector* d, at_detection* out, int cap_per_frame, int* n_
     int* idx = d->res_idx.data() + (size_t)f * kMaxDets;
     int n = 0;
     if (status & kStatusPairsCapped) rc = AT_E_CAPACITY;  // the first kMaxPairs pairs' detections are kept
-    if (status & (kStatusPairsOverflow | kStatusHashFull | kStatusPointsOverflow | kStatusQuadsOverflow | kStatusDetsOverflow)) {
+    if (d->mj_ent_batch && d->h_ent_info[(size_t)f * at::kEntInfoWords]) {
+      bad_entropy = true;  // the frame's entropy-coded data was bad: a flat plane went through, nothing is reported
+    } else if (status & (kStatusPairsOverflow | kStatusHashFull | kStatusPointsOverflow | kStatusQuadsOverflow | kStatusDetsOverflow)) {
       rc = AT_E_CAPACITY;
     } else {
       const DevDetection* cand = d->h_dets + (size_t)f * kDetPoolPerFrame;
@@ -886,7 +922,7 @@ static int collect(at_detector* d, at_detection* out, int cap_per_frame, int* n_
     if (n_per_frame) n_per_frame[f] = n;
   }
   d->host_tail_us += now_us() - t1;
-  return rc;
+  return bad_entropy ? AT_E_INVALID : rc;
 }
 
 static int check_fmt(int fmt) { return fmt == AT_FMT_YUYV || fmt == AT_FMT_BGR8 || fmt == AT_FMT_GRAY8; }
@@ -947,6 +983,10 @@ int at_detect(at_detector* d, const uint8_t* frame, at_pixfmt fmt, at_detection*
 // continues as host-fed GRAY8 frames (the captured launch sequence is the GRAY8 one).
 // With colour on (at_mjpg_set_color) the chroma coefficients travel behind the luma ones
 // and two more launches in front of the graph leave each frame's BGR8 image in d_mj_bgr.
+// With the device entropy decode on (at_mjpg_set_device_entropy) the host only parses the
+// markers: the batch's records (geometry, stream headers, decode tables, raw scan bytes) go
+// over in one copy, the slots are zeroed and k_mjpg_entropy writes the dense coefficients in
+// front of the same kernels; a frame with more than W * H scan bytes is decoded here as before.
 //
 // The buffers, allocated on first use.  color: the slots also hold the chroma sub-streams (worst case 4:4:4, all three planes
 // dense), and the chroma planes and BGR8 images exist.  Luma-only buffers from earlier
@@ -1014,9 +1054,66 @@ int at_mjpg_set_color(at_detector* d, int enable) {
   return AT_OK;
 }
 
+int at_mjpg_set_device_entropy(at_detector* d, int enable) {
+  if (!d) return AT_E_INVALID;
+  d->mj_dev_ent = enable ? 1 : 0;
+  return AT_OK;
+}
+
+int at_mjpg_set_subseq(at_detector* d, int bytes) {
+  if (!d || bytes < 16 || bytes > 256 || (bytes & (bytes - 1))) return AT_E_INVALID;
+  d->mj_subseq = bytes;
+  return AT_OK;
+}
+
+// The buffers of the device entropy decode, allocated on first use: the compressed input (a
+// directory of B offsets, then per frame at most a record and W * H scan bytes -- a larger
+// frame takes the host route) as two page-locked sets and a device copy, and the kernel's
+// scratch for the smallest piece size (16 bytes) and the most blocks a sampling decodes.
+static int mjpg_ent_prepare(at_detector* d) {
+  if (d->ent.in) return AT_OK;
+  const size_t B = (size_t)d->B, npix = (size_t)d->g.W * d->g.H;
+  const size_t dir = (B * 8 + 255) & ~(size_t)255;
+  const size_t per = (at::kEntRecordMax + npix + 16 + 255) & ~(size_t)255;
+  const size_t cap = dir + per * B;
+  const uint32_t pieces = (uint32_t)(npix / 16 + 1);
+  const uint32_t dcb = (uint32_t)at::ent_max_blocks(d->g.W, d->g.H);
+  uint8_t* h[2] = {nullptr, nullptr};
+  uint32_t* hinfo = nullptr;
+  void* dv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const size_t sz[6] = {cap, 8 * B * pieces, 8 * B * pieces, 4 * B * pieces, 2 * B * dcb, 4 * B * at::kEntInfoWords};
+  bool ok = hipHostMalloc((void**)&h[0], cap, hipHostMallocDefault) == hipSuccess &&
+            hipHostMalloc((void**)&h[1], cap, hipHostMallocDefault) == hipSuccess &&
+            hipHostMalloc((void**)&hinfo, sz[5], hipHostMallocDefault) == hipSuccess;
+  for (int i = 0; ok && i < 6; i++) ok = hipMalloc(&dv[i], sz[i]) == hipSuccess;
+  if (!ok) {
+    for (uint8_t* p : h)
+      if (p) (void)hipHostFree(p);
+    if (hinfo) (void)hipHostFree(hinfo);
+    for (void* p : dv)
+      if (p) (void)hipFree(p);
+    return AT_E_NOMEM;
+  }
+  for (void* p : dv) d->allocs.push_back(p);
+  memset(hinfo, 0, sz[5]);
+  d->mj_ent_host[0] = h[0];
+  d->mj_ent_host[1] = h[1];
+  d->mj_ent_cap = cap;
+  d->h_ent_info = hinfo;
+  d->ent.in = (const uint8_t*)dv[0];
+  d->ent.entry = (uint64_t*)dv[1];
+  d->ent.exit = (uint64_t*)dv[2];
+  d->ent.nblk = (uint32_t*)dv[3];
+  d->ent.pieces = pieces;
+  d->ent.dcdiff = (int16_t*)dv[4];
+  d->ent.dc_blocks = dcb;
+  d->ent.info = (uint32_t*)dv[5];
+  return AT_OK;
+}
+
 int at_mjpg_stats(at_detector* d, uint64_t* out, int cap) {
   if (!d || !out || cap < 1) return AT_E_INVALID;
-  const int n = std::min(cap, 6);
+  const int n = std::min(cap, 9);
   for (int i = 0; i < n; i++) out[i] = d->mj_stats[i];
   return n;
 }
@@ -1035,44 +1132,122 @@ int at_enqueue_mjpg(at_detector* d, const uint8_t* const* jpgs, const size_t* le
   if (prc != AT_OK) return prc;
   const int set = d->mj_cur ^ 1;
   uint8_t* stage = d->mj_host[set];
-  const double t0 = now_us();
-  const int nthr = std::min(d->mj_threads, nframes);
-  auto work = [&](int t) {
-    at::MjpgDecoder& dec = d->mj_dec[(size_t)t];
-    for (int f = t; f < nframes; f += nthr) {
-      int rc = dec.decode(jpgs[f], lens[f], d->g.W, d->g.H, color);
-      if (rc == AT_OK) {
-        d->mj_bytes[(size_t)f] = dec.packed_bytes();
-        rc = dec.pack(stage + (size_t)f * d->mj_slot, d->mj_slot);
-        d->mj_dense[(size_t)f] = dec.dense() ? 1 : 0;
-      }
-      d->mj_rc[(size_t)f] = rc;
-    }
-  };
-  if (nthr > 1) {
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nthr; t++) pool.emplace_back(work, t);
-    work(0);
-    for (auto& th : pool) th.join();
-  } else {
-    work(0);
+  const bool dev = d->mj_dev_ent != 0;
+  if (dev) {
+    const int erc = mjpg_ent_prepare(d);
+    if (erc != AT_OK) return erc;
   }
-  const double t1 = now_us();
-  for (int f = 0; f < nframes; f++)
-    if (d->mj_rc[(size_t)f] != AT_OK) {
-      if (bad_frame) *bad_frame = f;
-      return d->mj_rc[(size_t)f];  // nothing enqueued, the staging set in use untouched
+  uint64_t st[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const double t0 = now_us();
+  if (dev) {
+    // markers only: every frame's record and scan bytes into the staging set, back to back
+    // behind the directory; a frame with more than W * H scan bytes is decoded here instead
+    uint8_t* es = d->mj_ent_host[set];
+    uint64_t* dir = reinterpret_cast<uint64_t*>(es);
+    const size_t npix = (size_t)d->g.W * d->g.H;
+    size_t at = ((size_t)d->B * 8 + 255) & ~(size_t)255;
+    for (int f = 0; f < nframes; f++) {
+      size_t scan_pos = 0;
+      int rc = at::mjpg_entropy_parse(jpgs[f], lens[f], d->g.W, d->g.H, color, (uint32_t)d->mj_subseq, es + at,
+                                      &scan_pos);
+      d->mj_dense[(size_t)f] = 0;
+      if (rc == AT_OK && lens[f] - scan_pos > npix) {
+        at::MjpgDecoder& dec = d->mj_dec[0];
+        rc = dec.decode(jpgs[f], lens[f], d->g.W, d->g.H, color);
+        if (rc == AT_OK) {
+          d->mj_bytes[(size_t)f] = dec.packed_bytes();
+          rc = dec.pack(stage + (size_t)f * d->mj_slot, d->mj_slot);
+          d->mj_dense[(size_t)f] = dec.dense() ? 1 : 0;
+        }
+        dir[f] = 0;
+        st[7]++;
+      } else if (rc == AT_OK) {
+        at::EntGeom g;
+        memcpy(&g, es + at, sizeof(g));
+        const size_t so = at::ent_scan_off(g.ntab);
+        memcpy(es + at + so, jpgs[f] + scan_pos, g.scan_len);
+        dir[f] = at;
+        d->mj_bytes[(size_t)f] = 0;
+        at = (at + so + g.scan_len + 15) & ~(size_t)15;
+      }
+      if (rc != AT_OK) {
+        if (bad_frame) *bad_frame = f;
+        return rc;  // nothing enqueued, the staging sets in use untouched
+      }
     }
-  if (d->pending) HIPCHK(hipEventSynchronize(d->ev_done));  // the frame table and result buffers are reused
-  uint64_t st[6] = {0, 0, 0, (uint64_t)(t1 - t0), 0, 0};
-  for (int f = 0; f < nframes; f++) {
-    const size_t nbytes = d->mj_bytes[(size_t)f];
-    st[0] += lens[f];
-    st[1] += nbytes;
-    st[2] += d->mj_dense[(size_t)f];
-    HIPCHK(hipMemcpyAsync(d->d_mj + (size_t)f * d->mj_slot, stage + (size_t)f * d->mj_slot, nbytes,
-                          hipMemcpyHostToDevice, d->st));
-    d->h_ftab[f] = d->d_in + (size_t)f * d->in_stride;
+    st[3] = (uint64_t)(now_us() - t0);
+    if (d->pending) HIPCHK(hipEventSynchronize(d->ev_done));  // the frame table and result buffers are reused
+    // zero payloads for the kernel to write into, then what crosses the link
+    HIPCHK(hipMemsetAsync(d->d_mj, 0, d->mj_slot * (size_t)nframes, d->st));
+    HIPCHK(hipMemsetAsync(d->ent.info, 0, sizeof(uint32_t) * at::kEntInfoWords * (size_t)d->B, d->st));
+    HIPCHK(hipMemcpyAsync(const_cast<uint8_t*>(d->ent.in), es, at, hipMemcpyHostToDevice, d->st));
+    st[1] = at;
+    for (int f = 0; f < nframes; f++) {
+      st[0] += lens[f];
+      st[2] += d->mj_dense[(size_t)f];
+      if (!dir[f]) {
+        const size_t nbytes = d->mj_bytes[(size_t)f];
+        st[1] += nbytes;
+        HIPCHK(hipMemcpyAsync(d->d_mj + (size_t)f * d->mj_slot, stage + (size_t)f * d->mj_slot, nbytes,
+                              hipMemcpyHostToDevice, d->st));
+      }
+      d->h_ftab[f] = d->d_in + (size_t)f * d->in_stride;
+    }
+    const bool etimed = d->profiling != 0;
+    if (etimed) {
+      for (hipEvent_t& e : d->ev_ent)
+        if (!e) HIPCHK(hipEventCreateWithFlags(&e, kTimingEventFlags));
+      HIPCHK(hipEventRecord(d->ev_ent[0], d->st));
+    }
+    at::EntBufs eb = d->ent;
+    eb.in_bytes = d->mj_ent_cap;  // (what lies behind the bytes copied is never a frame's: its lengths bound it)
+    eb.coef = d->d_mj;
+    eb.slot = d->mj_slot;
+    eb.nb = (uint32_t)(d->g.W / 8) * (uint32_t)(d->g.H / 8);
+    HIPCHK(launch_mjpg_entropy(eb, nframes, d->st));
+    if (etimed) HIPCHK(hipEventRecord(d->ev_ent[1], d->st));
+    d->mj_ent_timed = etimed ? 1 : 0;
+    HIPCHK(hipMemcpyAsync(d->h_ent_info, d->ent.info, sizeof(uint32_t) * at::kEntInfoWords * (size_t)nframes,
+                          hipMemcpyDeviceToHost, d->st));
+  } else {
+    const int nthr = std::min(d->mj_threads, nframes);
+    auto work = [&](int t) {
+      at::MjpgDecoder& dec = d->mj_dec[(size_t)t];
+      for (int f = t; f < nframes; f += nthr) {
+        int rc = dec.decode(jpgs[f], lens[f], d->g.W, d->g.H, color);
+        if (rc == AT_OK) {
+          d->mj_bytes[(size_t)f] = dec.packed_bytes();
+          rc = dec.pack(stage + (size_t)f * d->mj_slot, d->mj_slot);
+          d->mj_dense[(size_t)f] = dec.dense() ? 1 : 0;
+        }
+        d->mj_rc[(size_t)f] = rc;
+      }
+    };
+    if (nthr > 1) {
+      std::vector<std::thread> pool;
+      for (int t = 1; t < nthr; t++) pool.emplace_back(work, t);
+      work(0);
+      for (auto& th : pool) th.join();
+    } else {
+      work(0);
+    }
+    const double t1 = now_us();
+    for (int f = 0; f < nframes; f++)
+      if (d->mj_rc[(size_t)f] != AT_OK) {
+        if (bad_frame) *bad_frame = f;
+        return d->mj_rc[(size_t)f];  // nothing enqueued, the staging set in use untouched
+      }
+    if (d->pending) HIPCHK(hipEventSynchronize(d->ev_done));  // the frame table and result buffers are reused
+    st[3] = (uint64_t)(t1 - t0);
+    for (int f = 0; f < nframes; f++) {
+      const size_t nbytes = d->mj_bytes[(size_t)f];
+      st[0] += lens[f];
+      st[1] += nbytes;
+      st[2] += d->mj_dense[(size_t)f];
+      HIPCHK(hipMemcpyAsync(d->d_mj + (size_t)f * d->mj_slot, stage + (size_t)f * d->mj_slot, nbytes,
+                            hipMemcpyHostToDevice, d->st));
+      d->h_ftab[f] = d->d_in + (size_t)f * d->in_stride;
+    }
   }
   d->mj_cur = set;
   const bool timed = d->profiling != 0;
@@ -1100,6 +1275,7 @@ int at_enqueue_mjpg(at_detector* d, const uint8_t* const* jpgs, const size_t* le
   d->last_staged = 1;
   d->last_mj_color = color;
   d->last_gp = color && d->prm.gp_c;
+  d->mj_ent_batch = dev;
   memcpy(d->mj_stats, st, sizeof(st));
   return AT_OK;
 }
@@ -1796,6 +1972,7 @@ int at_set_debug_taps(at_detector* d, int enable) {
 
 int at_frame_status(at_detector* d, int frame) {
   if (!d || frame < 0 || frame >= d->last_nframes) return AT_E_INVALID;
+  if (d->mj_ent_batch && !d->pending && d->h_ent_info[(size_t)frame * at::kEntInfoWords]) return AT_E_INVALID;
   const uint32_t s = d->h_ctrl[kCtlStatus * d->B + frame];
   return (s & (kStatusPairsOverflow | kStatusHashFull | kStatusPointsOverflow | kStatusQuadsOverflow | kStatusDetsOverflow |
                kStatusPairsCapped))

@@ -27,6 +27,7 @@
 #include "at_common.h"
 #include "at_gp.h"
 #include "at_mjpg.h"
+#include "at_mjpg_entropy.h"
 #include "at_pose.h"
 
 
@@ -5704,6 +5705,193 @@ hipError_t launch_mjpg_color(const uint8_t* coef, size_t slot, const uint8_t* gr
                      0, st, coef, slot, planes, plane_stride, nb);
   hipLaunchKernelGGL(k_mjpg_bgr, dim3((W / 4 + 63) / 64, (H + 3) / 4, nframes), dim3(64, 4), 0, st, coef, slot, gray,
                      planes, plane_stride, bgr, img_stride, W, H);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// MJPG input, entropy decode on the device (at_mjpg_set_device_entropy): the frame's raw
+// scan bytes in, the dense coefficient layout k_mjpg_idct reads out.  at_mjpg_entropy.h
+// has the algorithm, its bound and the arithmetic (shared with at_mjpg_entropy_host).
+//
+// One workgroup of 1024 threads per frame, thread t taking pieces t, t + 1024, ... of S
+// bytes each; four phases, a workgroup barrier between them, no grid-wide wait:
+//   synchronise  round 0 decodes every piece from a guessed state; in every later round a
+//                piece whose predecessor's exit state is not the state it was last decoded
+//                from decodes again.  The loop ends when a round changes nothing, at the
+//                latest after `pieces` rounds (truth advances a piece a round).  States and
+//                block counts live in HBM scratch (a 1080p frame at its largest has 32 K
+//                pieces), a round's reads and writes separated by barriers.
+//   place        exclusive scan of the pieces' block counts: each piece's first block.
+//   write        every piece once more from its (now true) entry state: non-zero AC
+//                coefficients to coef[raster(block)][natural(zig-zag)], DC differences of
+//                every decoded block to the DC scratch; restart markers and block counts
+//                are checked here.
+//   DC           segmented prefix sum (16-bit modular, segments at the restart intervals)
+//                of the differences in decode order, into coefficient 0.
+// The payloads were zeroed on the stream beforehand.  A frame with an error has its
+// payloads zeroed again and its error bits in info[0]; rounds go to info[1].
+// The decode diverges by nature (every lane its own bit stream); the tables (at most
+// 6 x 1424 B) are in LDS, the scan bytes come through L1/L2 as byte loads.
+// ---------------------------------------------------------------------------
+constexpr int kEntThreads = 1024;
+constexpr uint32_t kEntDirty = 0xffffffffu;
+
+__global__ __launch_bounds__(kEntThreads) void k_mjpg_entropy(EntBufs b) {
+  __shared__ __attribute__((aligned(16))) EntTab s_tab[kEntMaxTabs];
+  __shared__ EntGeom s_g;
+  __shared__ uint32_t s_scan[kEntThreads];
+  __shared__ EntDcSum s_dc[kEntThreads];
+  __shared__ int s_changed[2], s_err;
+  const uint32_t f = blockIdx.x, t = threadIdx.x;
+  const uint64_t off = reinterpret_cast<const uint64_t*>(b.in)[f];
+  if (!off) return;  // the host decoded this frame
+  uint32_t* info = b.info + (size_t)f * kEntInfoWords;
+  if (off + kEntRecordMax > b.in_bytes || (off & 15)) {
+    if (t == 0) info[0] = kEntErrGeom;
+    return;
+  }
+  const uint8_t* rec = b.in + off;
+  if (t < sizeof(EntGeom) / 4) reinterpret_cast<uint32_t*>(&s_g)[t] = reinterpret_cast<const uint32_t*>(rec)[t];
+  if (t == 0) s_changed[0] = s_changed[1] = s_err = 0;
+  __syncthreads();
+  const EntGeom g = s_g;
+  const EntLayout L = ent_layout(g);
+  const uint32_t np = ent_pieces(g), total = ent_total_blocks(g), nmcu = g.mcux * g.mcuy;
+  // (the host wrote the record; the checks keep a wrong one inside the buffers all the same)
+  if (!ent_geom_ok(g) || L.nb != b.nb || L.total > b.slot || L.cb_off != g.cb_off ||
+      L.cr_off != g.cr_off || np > b.pieces || total > b.dc_blocks ||
+      off + ent_scan_off(g.ntab) + g.scan_len > b.in_bytes) {
+    if (t == 0) info[0] = kEntErrGeom;
+    return;
+  }
+  uint8_t* slot = b.coef + (size_t)f * b.slot;
+  {
+    // tables to LDS, stream headers to the coefficient slot
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(rec + kEntTabsOff);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(s_tab);
+    for (uint32_t i = t; i < g.ntab * (uint32_t)(sizeof(EntTab) / 4); i += kEntThreads) dst[i] = src[i];
+    const uint32_t* hs = reinterpret_cast<const uint32_t*>(rec + kEntHdrsOff);
+    const uint32_t c = t >> 6, w = t & 63;  // header c, word w
+    if (c == 0) reinterpret_cast<uint32_t*>(slot)[w] = hs[w];
+    else if (c < 3 && L.cnb) reinterpret_cast<uint32_t*>(slot + (c == 1 ? L.cb_off : L.cr_off))[w] = hs[64 * c + w];
+  }
+  __syncthreads();
+  const EntCtx c = ent_ctx(g, s_tab, rec + ent_scan_off(g.ntab));
+  uint64_t* entry = b.entry + (size_t)f * b.pieces;
+  uint64_t* exitv = b.exit + (size_t)f * b.pieces;
+  uint32_t* nblk = b.nblk + (size_t)f * b.pieces;
+
+  // ---- synchronise
+  for (uint32_t i = t; i < np; i += kEntThreads) {
+    const EntState s0 = ent_guess(c, i);
+    EntCount cnt;
+    entry[i] = ent_pack(s0);
+    exitv[i] = ent_pack(ent_decode_piece(c, s0, ent_piece_end(c, i, np), cnt));
+    nblk[i] = cnt.blocks;
+  }
+  __syncthreads();
+  uint32_t rounds = 1;
+  for (uint32_t r = 1; r <= np; r++) {  // truth advances a piece a round: np rounds at the most
+    bool any = false;
+    for (uint32_t i = t; i < np; i += kEntThreads)
+      if (i) {
+        const uint64_t e = exitv[i - 1];
+        if (e != entry[i]) {
+          entry[i] = e;
+          nblk[i] = kEntDirty;
+          any = true;
+        }
+      }
+    if (any) s_changed[r & 1] = 1;
+    __syncthreads();
+    if (!s_changed[r & 1]) break;
+    if (t == 0) s_changed[(r + 1) & 1] = 0;
+    for (uint32_t i = t; i < np; i += kEntThreads)
+      if (nblk[i] == kEntDirty) {
+        EntCount cnt;
+        exitv[i] = ent_pack(ent_decode_piece(c, ent_unpack(entry[i]), ent_piece_end(c, i, np), cnt));
+        nblk[i] = cnt.blocks;
+      }
+    rounds++;
+    __syncthreads();
+  }
+
+  // ---- place: thread t sums pieces [p0, p1), the workgroup scans the sums
+  const uint32_t per = (np + kEntThreads - 1) / kEntThreads;
+  const uint32_t p0 = min(np, t * per), p1 = min(np, p0 + per);
+  uint32_t mine = 0;
+  for (uint32_t i = p0; i < p1; i++) mine += min(nblk[i], total + 1);
+  mine = min(mine, total + 1);  // (anything above the picture's blocks is "behind it")
+  s_scan[t] = mine;
+  __syncthreads();
+  for (uint32_t d = 1; d < kEntThreads; d <<= 1) {
+    const uint32_t a = t >= d ? s_scan[t - d] : 0;
+    __syncthreads();
+    s_scan[t] = min(s_scan[t] + a, total + 1);
+    __syncthreads();
+  }
+  {
+    uint32_t run = t ? s_scan[t - 1] : 0;
+    for (uint32_t i = p0; i < p1; i++) {
+      const uint32_t n = nblk[i];
+      nblk[i] = run;
+      run = min(run + min(n, total + 1), total + 1);
+    }
+  }
+  const uint32_t begun = s_scan[kEntThreads - 1];
+  __syncthreads();
+
+  // ---- write
+  EntOut o;
+  o.luma = reinterpret_cast<int16_t*>(slot + kMjpgHdrBytes);
+  o.chroma[0] = L.cnb ? reinterpret_cast<int16_t*>(slot + L.cb_off + kMjpgHdrBytes) : nullptr;
+  o.chroma[1] = L.cnb ? reinterpret_cast<int16_t*>(slot + L.cr_off + kMjpgHdrBytes) : nullptr;
+  o.dcdiff = b.dcdiff + (size_t)f * b.dc_blocks;
+  for (uint32_t i = t; i < np; i += kEntThreads) {
+    const EntState s = ent_unpack(entry[i]);
+    EntWrite w(&c, o, nblk[i], s.zz != 0);
+    ent_decode_piece(c, s, ent_piece_end(c, i, np), w);
+    if (w.err) atomicOr(&s_err, w.err);
+  }
+  if (t == 0 && begun < total) atomicOr(&s_err, (int)kEntErrBlocks);
+  __syncthreads();
+  const int err = s_err;
+  if (err) {
+    // a frame with bad entropy data: all coefficients zero (a flat plane), the error reported
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    for (uint32_t i = t; i < L.nb * 8u; i += kEntThreads) reinterpret_cast<uint4*>(slot + kMjpgHdrBytes)[i] = z;
+    for (uint32_t i = t; i < L.cnb * 8u; i += kEntThreads) {
+      reinterpret_cast<uint4*>(slot + L.cb_off + kMjpgHdrBytes)[i] = z;
+      reinterpret_cast<uint4*>(slot + L.cr_off + kMjpgHdrBytes)[i] = z;
+    }
+    if (t == 0) {
+      info[0] = (uint32_t)err;
+      info[1] = rounds;
+    }
+    return;
+  }
+
+  // ---- DC: thread t sums MCUs [m0, m1), the workgroup scans, thread t applies
+  const uint32_t mper = (nmcu + kEntThreads - 1) / kEntThreads;
+  const uint32_t m0 = min(nmcu, t * mper), m1 = min(nmcu, m0 + mper);
+  EntDcSum zero;
+  zero.s[0] = zero.s[1] = zero.s[2] = zero.reset = 0;
+  s_dc[t] = ent_dc_range(c, o, m0, m1, false, zero);
+  __syncthreads();
+  for (uint32_t d = 1; d < kEntThreads; d <<= 1) {
+    EntDcSum a = zero;
+    if (t >= d) a = s_dc[t - d];
+    __syncthreads();
+    if (t >= d) s_dc[t] = ent_dc_join(a, s_dc[t]);
+    __syncthreads();
+  }
+  ent_dc_range(c, o, m0, m1, true, t ? s_dc[t - 1] : zero);
+  if (t == 0) info[1] = rounds;
+}
+
+// after the payloads were zeroed and the batch's bytes copied, on the same stream
+hipError_t launch_mjpg_entropy(const EntBufs& b, int nframes, hipStream_t st) {
+  hipLaunchKernelGGL(k_mjpg_entropy, dim3(nframes), dim3(kEntThreads), 0, st, b);
   return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // (at_mjpg.h).  Every read of the input is checked against its length; the decode
 // loops are bounded by the picture's block count, so no input can make them spin.
 #include "at_mjpg.h"
+#include "at_mjpg_entropy.h"
 
 #include <string.h>
 
@@ -155,27 +156,26 @@ struct Comp {
   int id, h, v, tq, td, ta;
 };
 
-}  // namespace
-
-uint32_t MjpgDecoder::decode_index(int bx, int by) const {
-  // decode order of luma block (bx, by): MCU by MCU, hs x vs blocks in each
-  const int hs = info_.hs, vs = info_.vs;
-  const int mcux = gw_ / hs;
-  const int mx = bx / hs, my = by / vs;
-  return (uint32_t)(((my * mcux + mx) * vs + by % vs) * hs + bx % hs);
-}
-
-int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h, bool keep_chroma) {
-  info_ = MjpgInfo{};
-  bw_ = bh_ = gw_ = gh_ = 0;
-  kept_tokens_ = 0;
-  chroma_ = false;
-  cbw_ = cbh_ = 0;
-  if (!jpg || len < 4 || jpg[0] != 0xff || jpg[1] != 0xd8) return kMjpgInvalid;
+// What the marker parser leaves for the entropy decode (host or device).
+struct Parsed {
   uint8_t qt[4][64];
   bool qt_def[4] = {false, false, false, false};
   Huff dc[4], ac[4];
   Comp comp[3] = {};
+  size_t scan_pos = 0;   // first byte of the scan data
+  bool header_only = false;
+};
+
+// SOI .. SOS: sizes, sampling, tables (a slot no DHT filled takes the Annex K table of its
+// kind).  want_w < 0: stops after the frame header (header_only).
+int mjpg_parse(const uint8_t* jpg, size_t len, int want_w, int want_h, MjpgInfo* info, Parsed* P) {
+  if (!jpg || len < 4 || jpg[0] != 0xff || jpg[1] != 0xd8) return kMjpgInvalid;
+  uint8_t (&qt)[4][64] = P->qt;
+  bool (&qt_def)[4] = P->qt_def;
+  Huff (&dc)[4] = P->dc;
+  Huff (&ac)[4] = P->ac;
+  Comp (&comp)[3] = P->comp;
+  P->header_only = false;
   bool have_sof = false;
   size_t pos = 2;
   for (;;) {
@@ -214,15 +214,18 @@ int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h, 
         for (int i = 1; i < 3; i++)
           if (comp[i].h != 1 || comp[i].v != 1) return kMjpgUnsupported;
       }
-      info_.width = w;
-      info_.height = h;
-      info_.ncomp = nf;
-      info_.hs = comp[0].h;
-      info_.vs = comp[0].v;
+      info->width = w;
+      info->height = h;
+      info->ncomp = nf;
+      info->hs = comp[0].h;
+      info->vs = comp[0].v;
       have_sof = true;
       if ((want_w > 0 && w != want_w) || (want_h > 0 && h != want_h)) return kMjpgInvalid;
       if ((size_t)w * (size_t)h > kMjpgMaxPixels) return kMjpgInvalid;
-      if (want_w < 0) return kMjpgOk;  // header only
+      if (want_w < 0) {  // header only
+        P->header_only = true;
+        return kMjpgOk;
+      }
     } else if ((m >= 0xc1 && m <= 0xcf) && m != 0xc4 && m != 0xc8) {
       return kMjpgUnsupported;  // extended, progressive, lossless, arithmetic (SOFn, DAC)
     } else if (m == 0xdb) {  // DQT
@@ -249,12 +252,12 @@ int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h, 
       }
     } else if (m == 0xdd) {  // DRI
       if (n != 2) return kMjpgInvalid;
-      info_.restart = (int)be16(s);
+      info->restart = (int)be16(s);
     } else if (m == 0xda) {  // SOS
       if (!have_sof || n < 1) return kMjpgInvalid;
       const int ns = s[0];
       if (ns < 1 || ns > 4 || n != (size_t)(4 + 2 * ns)) return kMjpgInvalid;
-      if (ns != info_.ncomp) return kMjpgUnsupported;  // one scan holds every component
+      if (ns != info->ncomp) return kMjpgUnsupported;  // one scan holds every component
       for (int i = 0; i < ns; i++) {
         if (s[1 + 2 * i] != comp[i].id) return kMjpgUnsupported;
         comp[i].td = s[2 + 2 * i] >> 4;
@@ -269,20 +272,49 @@ int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h, 
 
   // tables the scan names; a slot no DHT filled takes the Annex K table of its kind
   if (!qt_def[comp[0].tq]) return kMjpgInvalid;
-  for (int i = 0; i < info_.ncomp; i++) {
+  for (int i = 0; i < info->ncomp; i++) {
     Huff& hd = dc[comp[i].td];
     Huff& ha = ac[comp[i].ta];
     if (!hd.defined) {
       if (comp[i].td > 1) return kMjpgInvalid;
       huff_build(&hd, comp[i].td ? kStdDcChrBits : kStdDcLumBits, kStdDcVals, 12);
-      info_.default_dht = 1;
+      info->default_dht = 1;
     }
     if (!ha.defined) {
       if (comp[i].ta > 1) return kMjpgInvalid;
       huff_build(&ha, comp[i].ta ? kStdAcChrBits : kStdAcLumBits, comp[i].ta ? kStdAcChrVals : kStdAcLumVals, 162);
-      info_.default_dht = 1;
+      info->default_dht = 1;
     }
   }
+  P->scan_pos = pos;
+  return kMjpgOk;
+}
+
+}  // namespace
+
+uint32_t MjpgDecoder::decode_index(int bx, int by) const {
+  // decode order of luma block (bx, by): MCU by MCU, hs x vs blocks in each
+  const int hs = info_.hs, vs = info_.vs;
+  const int mcux = gw_ / hs;
+  const int mx = bx / hs, my = by / vs;
+  return (uint32_t)(((my * mcux + mx) * vs + by % vs) * hs + bx % hs);
+}
+
+int MjpgDecoder::decode(const uint8_t* jpg, size_t len, int want_w, int want_h, bool keep_chroma) {
+  info_ = MjpgInfo{};
+  bw_ = bh_ = gw_ = gh_ = 0;
+  kept_tokens_ = 0;
+  chroma_ = false;
+  cbw_ = cbh_ = 0;
+  Parsed P;
+  const int prc = mjpg_parse(jpg, len, want_w, want_h, &info_, &P);
+  if (prc != kMjpgOk || P.header_only) return prc;
+  const uint8_t (&qt)[4][64] = P.qt;
+  const bool (&qt_def)[4] = P.qt_def;
+  const Huff (&dc)[4] = P.dc;
+  const Huff (&ac)[4] = P.ac;
+  const Comp (&comp)[3] = P.comp;
+  const size_t pos = P.scan_pos;
   for (int k = 0; k < 64; k++) q_[kZigzag[k]] = qt[comp[0].tq][k];
   const bool chroma = keep_chroma && info_.ncomp == 3;
   if (chroma)
@@ -396,9 +428,9 @@ bool MjpgDecoder::plane_dense(const Plane& p) {
   return 4 * (nb + 1) + 4 * (size_t)p.kept >= 128 * nb;
 }
 
-size_t MjpgDecoder::plane_bytes(const Plane& p) {
+size_t MjpgDecoder::plane_bytes(const Plane& p, bool force_dense) {
   const size_t nb = (size_t)p.bw * p.bh;
-  return (size_t)kMjpgHdrBytes + (plane_dense(p) ? 128 * nb : 4 * (nb + 1) + 4 * (size_t)p.kept);
+  return (size_t)kMjpgHdrBytes + (force_dense || plane_dense(p) ? 128 * nb : 4 * (nb + 1) + 4 * (size_t)p.kept);
 }
 
 bool MjpgDecoder::dense() const { return plane_dense(plane(0)); }
@@ -412,15 +444,22 @@ size_t MjpgDecoder::packed_bytes() const {
   return n;
 }
 
+size_t MjpgDecoder::dense_bytes() const {
+  size_t n = plane_bytes(plane(0), true);
+  if (chroma_ && cbw_)
+    for (int c = 1; c < 3; c++) n = sub_align(n) + plane_bytes(plane(c), true);
+  return n;
+}
+
 size_t MjpgDecoder::slot_bytes(int w, int h, bool color) {
   const size_t one = (size_t)kMjpgHdrBytes + 128 * (size_t)((w + 7) / 8) * (size_t)((h + 7) / 8);
   return color ? 3 * sub_align(one) : one;
 }
 
 // header (q, mode, token count, block count) and payload of one plane
-void MjpgDecoder::pack_plane(const Plane& p, uint8_t* dst) const {
+void MjpgDecoder::pack_plane(const Plane& p, uint8_t* dst, bool force_dense) const {
   const uint32_t nb = (uint32_t)(p.bw * p.bh);
-  const bool dn = plane_dense(p);
+  const bool dn = force_dense || plane_dense(p);
   memset(dst, 0, kMjpgHdrBytes);
   memcpy(dst, p.q, 64 * sizeof(uint16_t));
   const uint32_t mode = dn ? kMjpgDense : kMjpgSparse, ntok = dn ? 0 : p.kept;
@@ -454,28 +493,32 @@ void MjpgDecoder::pack_plane(const Plane& p, uint8_t* dst) const {
   off[nb] = o;
 }
 
-int MjpgDecoder::pack(uint8_t* dst, size_t cap) const {
+int MjpgDecoder::pack(uint8_t* dst, size_t cap) const { return pack_all(dst, cap, false); }
+int MjpgDecoder::pack_dense(uint8_t* dst, size_t cap) const { return pack_all(dst, cap, true); }
+
+int MjpgDecoder::pack_all(uint8_t* dst, size_t cap, bool fd) const {
   const uint32_t nb = nblocks();
-  if (!dst || !nb || start_.size() != (size_t)gw_ * gh_ + 1 || cap < packed_bytes()) return kMjpgInvalid;
-  pack_plane(plane(0), dst);
+  if (!dst || !nb || start_.size() != (size_t)gw_ * gh_ + 1 || cap < (fd ? dense_bytes() : packed_bytes()))
+    return kMjpgInvalid;
+  pack_plane(plane(0), dst, fd);
   if (!chroma_) return kMjpgOk;
   // colour on: the sampling word, then the chroma sub-streams behind the luma stream
   const uint32_t samp = (uint32_t)info_.hs | ((uint32_t)info_.vs << 8) | ((uint32_t)info_.ncomp << 16);
   memcpy(dst + kMjpgSampOff, &samp, 4);
   if (!cbw_) return kMjpgOk;  // a single-component frame: no sub-streams, offsets 0
-  size_t at = plane_bytes(plane(0));
+  size_t at = plane_bytes(plane(0), fd);
   for (int c = 1; c < 3; c++) {
     const Plane p = plane(c);
     if (cstart_[c - 1].size() != (size_t)cbw_ * cbh_ + 1) return kMjpgInvalid;
     const size_t sub = sub_align(at);
     memset(dst + at, 0, sub - at);
-    pack_plane(p, dst + sub);
+    pack_plane(p, dst + sub, fd);
     const uint32_t off32 = (uint32_t)sub, bw = (uint32_t)cbw_, hs = (uint32_t)info_.hs, vs = (uint32_t)info_.vs;
     memcpy(dst + (c == 1 ? kMjpgCbOff : kMjpgCrOff), &off32, 4);
     memcpy(dst + sub + kMjpgBwOff, &bw, 4);
     memcpy(dst + sub + kMjpgHsOff, &hs, 4);
     memcpy(dst + sub + kMjpgVsOff, &vs, 4);
-    at = sub + plane_bytes(p);
+    at = sub + plane_bytes(p, fd);
   }
   return kMjpgOk;
 }
@@ -596,6 +639,179 @@ extern "C" int at_mjpg_stream_mode_host(const uint8_t* jpg, size_t len, int want
   if (rc != at::kMjpgOk) return rc;
   if (stream_bytes) *stream_bytes = dec.packed_bytes();
   return dec.dense() ? 1 : 0;
+}
+
+// ---- device entropy decode: the marker parse, and the algorithm run on the host ----------
+namespace at {
+
+int mjpg_entropy_parse(const uint8_t* jpg, size_t len, int want_w, int want_h, bool keep_chroma, uint32_t subseq,
+                       uint8_t* rec, size_t* scan_pos) {
+  MjpgInfo info{};
+  Parsed P;
+  const int rc = mjpg_parse(jpg, len, want_w > 0 ? want_w : 0, want_h > 0 ? want_h : 0, &info, &P);
+  if (rc != kMjpgOk) return rc;
+  const bool chroma = keep_chroma && info.ncomp == 3;
+  if (chroma)
+    for (int c = 1; c < 3; c++)
+      if (!P.qt_def[P.comp[c].tq]) return kMjpgInvalid;
+  if (len - P.scan_pos > 0xfffffff0u) return kMjpgInvalid;
+  EntGeom g{};
+  g.scan_len = (uint32_t)(len - P.scan_pos);
+  g.ncomp = (uint32_t)info.ncomp;
+  g.hs = (uint32_t)info.hs;
+  g.vs = (uint32_t)info.vs;
+  g.bw = (uint32_t)((info.width + 7) / 8);
+  g.bh = (uint32_t)((info.height + 7) / 8);
+  g.mcux = (g.bw + g.hs - 1) / g.hs;
+  g.mcuy = (g.bh + g.vs - 1) / g.vs;
+  g.restart = (uint32_t)info.restart;
+  g.keep_chroma = chroma ? 1 : 0;
+  g.subseq = subseq;
+  // the tables the scan names, each once
+  EntTab* tabs = reinterpret_cast<EntTab*>(rec + kEntTabsOff);
+  int slot_of[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};
+  for (int i = 0; i < info.ncomp; i++)
+    for (int cls = 0; cls < 2; cls++) {
+      const int id = cls ? P.comp[i].ta : P.comp[i].td;
+      if (slot_of[cls][id] < 0) {
+        const Huff& h = cls ? P.ac[id] : P.dc[id];
+        EntTab t;
+        memset(&t, 0, sizeof(t));
+        memcpy(t.look, h.look, sizeof(t.look));
+        memcpy(t.maxcode + 1, h.maxcode + 1, 17 * sizeof(int32_t));
+        memcpy(t.valoff + 1, h.valoff + 1, 16 * sizeof(int32_t));
+        memcpy(t.vals, h.vals, sizeof(t.vals));
+        memcpy(&tabs[g.ntab], &t, sizeof(t));
+        slot_of[cls][id] = (int)g.ntab++;
+      }
+      g.tabsel |= (uint32_t)slot_of[cls][id] << (4 * (2 * i + cls));
+    }
+  const EntLayout L = ent_layout(g);
+  g.cb_off = L.cb_off;
+  g.cr_off = L.cr_off;
+  memcpy(rec, &g, sizeof(g));
+  // the stream headers, as pack() writes them for dense planes
+  uint8_t* hdr = rec + kEntHdrsOff;
+  memset(hdr, 0, 3 * (size_t)kMjpgHdrBytes);
+  for (int c = 0; c < (L.cnb ? 3 : 1); c++) {
+    uint8_t* h = hdr + (size_t)c * kMjpgHdrBytes;
+    uint16_t q[64];
+    for (int k = 0; k < 64; k++) q[kZigzag[k]] = P.qt[P.comp[c].tq][k];
+    memcpy(h, q, sizeof(q));
+    const uint32_t mode = kMjpgDense, nb = c ? L.cnb : L.nb;
+    memcpy(h + kMjpgModeOff, &mode, 4);
+    memcpy(h + kMjpgNblkOff, &nb, 4);
+    if (c) {
+      memcpy(h + kMjpgBwOff, &g.mcux, 4);
+      memcpy(h + kMjpgHsOff, &g.hs, 4);
+      memcpy(h + kMjpgVsOff, &g.vs, 4);
+    }
+  }
+  if (keep_chroma) {
+    const uint32_t samp = g.hs | (g.vs << 8) | (g.ncomp << 16);
+    memcpy(hdr + kMjpgSampOff, &samp, 4);
+    memcpy(hdr + kMjpgCbOff, &L.cb_off, 4);
+    memcpy(hdr + kMjpgCrOff, &L.cr_off, 4);
+  }
+  *scan_pos = P.scan_pos;
+  return kMjpgOk;
+}
+
+}  // namespace at
+
+extern "C" int at_mjpg_entropy_host(const uint8_t* jpg, size_t len, int want_w, int want_h, int subseq_bytes,
+                                    int keep_chroma, uint8_t* out, size_t cap, int* rounds) {
+  using namespace at;
+  if (rounds) *rounds = 0;
+  if (subseq_bytes < 1) return kMjpgInvalid;  // (the kernel's pieces are 16 bytes or more; any size goes here)
+  std::vector<uint8_t> rec(kEntRecordMax);
+  size_t scan_pos = 0;
+  // (any piece size goes here; one larger than the scan is one piece: the serial decode)
+  const int rc = mjpg_entropy_parse(jpg, len, want_w, want_h, keep_chroma != 0, (uint32_t)subseq_bytes, rec.data(),
+                                    &scan_pos);
+  if (rc != kMjpgOk) return rc;
+  EntGeom g;
+  memcpy(&g, rec.data(), sizeof(g));
+  const EntLayout L = ent_layout(g);
+  if (!out || cap < L.total) return kMjpgInvalid;
+  std::vector<EntTab> tabs(g.ntab);
+  memcpy(tabs.data(), rec.data() + kEntTabsOff, g.ntab * sizeof(EntTab));
+  const EntCtx c = ent_ctx(g, tabs.data(), jpg + scan_pos);
+  const uint32_t np = ent_pieces(g), total = ent_total_blocks(g);
+
+  // synchronise: round 0 from the guesses, then whoever's entry changed decodes again
+  std::vector<uint64_t> entry(np), exitv(np);
+  std::vector<uint32_t> nblk(np);
+  std::vector<uint8_t> dirty(np, 0);
+  auto run = [&](uint32_t i) {
+    EntCount cnt;
+    exitv[i] = ent_pack(ent_decode_piece(c, ent_unpack(entry[i]), ent_piece_end(c, i, np), cnt));
+    nblk[i] = cnt.blocks;
+  };
+  for (uint32_t i = 0; i < np; i++) {
+    EntState s0 = ent_guess(c, i);
+    entry[i] = ent_pack(s0);
+    run(i);
+  }
+  int nrounds = 1;
+  for (uint32_t r = 1; r <= np; r++) {  // truth advances a piece a round: np rounds at the most
+    bool changed = false;
+    for (uint32_t i = 1; i < np; i++)
+      if ((dirty[i] = exitv[i - 1] != entry[i])) {
+        entry[i] = exitv[i - 1];
+        changed = true;
+      }
+    if (!changed) break;
+    for (uint32_t i = 1; i < np; i++)
+      if (dirty[i]) run(i);
+    nrounds++;
+  }
+  if (rounds) *rounds = nrounds;
+
+  // place: each piece's first block; write: once more from the true states
+  memset(out, 0, L.total);
+  std::vector<int16_t> dcdiff(total ? total : 1, 0);
+  EntOut o;
+  o.luma = reinterpret_cast<int16_t*>(out + kMjpgHdrBytes);
+  o.chroma[0] = L.cnb ? reinterpret_cast<int16_t*>(out + L.cb_off + kMjpgHdrBytes) : nullptr;
+  o.chroma[1] = L.cnb ? reinterpret_cast<int16_t*>(out + L.cr_off + kMjpgHdrBytes) : nullptr;
+  o.dcdiff = dcdiff.data();
+  int err = 0;
+  uint64_t first = 0;
+  for (uint32_t i = 0; i < np; i++) {
+    const EntState s = ent_unpack(entry[i]);
+    // (pieces behind the picture's last block decode whatever follows it, into nothing)
+    const uint32_t f32 = first > total ? total + 1 : (uint32_t)first;
+    EntWrite w(&c, o, f32, s.zz != 0);
+    ent_decode_piece(c, s, ent_piece_end(c, i, np), w);
+    err |= w.err;
+    first += nblk[i];
+  }
+  if (first < total) err |= kEntErrBlocks;
+  if (err) {
+    memset(out, 0, L.total);
+    return kMjpgInvalid;
+  }
+  // DC: the segmented prefix sum, here as one range
+  EntDcSum zero{};
+  ent_dc_range(c, o, 0, g.mcux * g.mcuy, true, zero);
+  memcpy(out, rec.data() + kEntHdrsOff, kMjpgHdrBytes);
+  if (L.cnb) {
+    memcpy(out + L.cb_off, rec.data() + kEntHdrsOff + kMjpgHdrBytes, kMjpgHdrBytes);
+    memcpy(out + L.cr_off, rec.data() + kEntHdrsOff + 2 * (size_t)kMjpgHdrBytes, kMjpgHdrBytes);
+  }
+  return kMjpgOk;
+}
+
+extern "C" int at_mjpg_dense_host(const uint8_t* jpg, size_t len, int want_w, int want_h, int keep_chroma,
+                                  uint8_t* out, size_t cap, size_t* out_bytes) {
+  at::MjpgDecoder dec;
+  if (out_bytes) *out_bytes = 0;
+  const int rc = dec.decode(jpg, len, want_w > 0 ? want_w : 0, want_h > 0 ? want_h : 0, keep_chroma != 0);
+  if (rc != at::kMjpgOk) return rc;
+  if (out_bytes) *out_bytes = dec.dense_bytes();
+  if (!out) return at::kMjpgOk;
+  return dec.pack_dense(out, cap);
 }
 
 // ---- JPEG output: tables, header and the sequential host encoder ------------------------

@@ -10,6 +10,10 @@
 // coefficients are kept too and travel as two more sub-streams behind the luma
 // one; k_mjpg_idct_chroma and k_mjpg_bgr then produce the BGR8 image.
 //
+// With at_mjpg_set_device_entropy the host stops after the marker parse and the Huffman
+// decode runs on the GPU as well (at_mjpg_entropy.h, k_mjpg_entropy), which leaves the
+// dense layout below in the frame's slot.
+//
 // Plain C++17, no HIP include: compiles alone with the host compiler (the
 // sanitized stand-alone check tests/mjpg_host_check.cpp builds it that way).
 //
@@ -310,6 +314,10 @@ class MjpgDecoder {
   // Writes the coefficient stream of the decoded frame to dst (cap bytes, at least
   // packed_bytes(); slot_bytes() of the picture's size always suffices).
   int pack(uint8_t* dst, size_t cap) const;
+  // The same with every plane in the dense encoding whatever its size (what the device
+  // entropy decode leaves in the slot, at_mjpg_entropy.h): dense_bytes() bytes.
+  size_t dense_bytes() const;
+  int pack_dense(uint8_t* dst, size_t cap) const;
   // The most a frame of w x h pixels can take (every plane dense; colour: 4:4:4).
   static size_t slot_bytes(int w, int h, bool color);
   // Full host decode: the luma plane (width x height) through the same integer IDCT.
@@ -348,8 +356,9 @@ class MjpgDecoder {
     return p.luma ? decode_index(bx, by) : (uint32_t)(by * p.bw + bx);
   }
   static bool plane_dense(const Plane& p);
-  static size_t plane_bytes(const Plane& p);
-  void pack_plane(const Plane& p, uint8_t* dst) const;
+  static size_t plane_bytes(const Plane& p, bool force_dense = false);
+  void pack_plane(const Plane& p, uint8_t* dst, bool force_dense = false) const;
+  int pack_all(uint8_t* dst, size_t cap, bool force_dense) const;
   // IDCT of the plane's blocks into out (row stride `stride`), cropped to w x h
   void idct_plane(const Plane& p, uint8_t* out, size_t stride, int w, int h) const;
 };

@@ -41,6 +41,7 @@ EXPORTS = [
     "at_encode_jpeg_device", "at_annotate_jpeg", "at_jpeg_max_bytes", "at_jpeg_stats", "at_jpeg_encode_host",
     "at_gp_parse_host", "at_gp_parse_device", "at_gp_draw_boxes_device", "at_gp_parse_stats",
     "at_gp_annotate_staged", "at_gp_annotate_jpeg", "at_gp_copy_raw",
+    "at_mjpg_set_device_entropy", "at_mjpg_set_subseq", "at_mjpg_entropy_host", "at_mjpg_dense_host",
 ]
 AT_GP_MAX_CANDIDATES = 4096
 # at_gp_box as a numpy record (the bit-exact view of what the library wrote)
@@ -224,6 +225,13 @@ def load_library(path: str = LIB_PATH):
         L.at_mjpg_copy_bgr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.at_mjpg_decode_bgr_host.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
                                               C.POINTER(C.c_int)]
+    if hasattr(L, "at_mjpg_set_device_entropy"):  # (A/B builds of older sources lack the device entropy decode)
+        L.at_mjpg_set_device_entropy.argtypes = [C.c_void_p, C.c_int]
+        L.at_mjpg_set_subseq.argtypes = [C.c_void_p, C.c_int]
+        L.at_mjpg_entropy_host.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_size_t, C.POINTER(C.c_int)]
+        L.at_mjpg_dense_host.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                         C.POINTER(C.c_size_t)]
     if hasattr(L, "at_annotate_jpeg"):  # (A/B builds of older sources lack the JPEG output)
         L.at_encode_jpeg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                             C.POINTER(C.c_size_t)]
@@ -347,6 +355,45 @@ def mjpg_stream_mode(jpg: bytes, width: int = 0, height: int = 0):
     if rc < 0:
         raise MjpgError("at_mjpg_stream_mode_host", rc)
     return ("dense" if rc else "sparse"), n.value
+
+
+def mjpg_dense_host(jpg: bytes, width: int = 0, height: int = 0, keep_chroma=False):
+    """at_mjpg_dense_host: the frame's coefficient streams as the serial host decoder gives
+    them, every plane dense (uint8 array: headers and payloads, the layout of at_mjpg.h)."""
+    L = load_library()
+    jpg = bytes(jpg)
+    n = C.c_size_t()
+    rc = L.at_mjpg_dense_host(jpg, len(jpg), int(width), int(height), int(bool(keep_chroma)), None, 0, C.byref(n))
+    if rc < 0:
+        raise MjpgError("at_mjpg_dense_host", rc)
+    out = np.empty(n.value, np.uint8)
+    rc = L.at_mjpg_dense_host(jpg, len(jpg), int(width), int(height), int(bool(keep_chroma)), out.ctypes.data,
+                              out.size, C.byref(n))
+    if rc < 0:
+        raise MjpgError("at_mjpg_dense_host", rc)
+    return out
+
+
+def mjpg_entropy_host(jpg: bytes, subseq_bytes: int, width: int = 0, height: int = 0, keep_chroma=False, nbytes=None):
+    """at_mjpg_entropy_host: the same streams from the parallel subsequence algorithm of
+    k_mjpg_entropy, run on the host piece by piece -> (uint8 array, rounds).  `nbytes`: the
+    streams' size where the caller knows it (else the serial decoder is asked)."""
+    L = load_library()
+    jpg = bytes(jpg)
+    if nbytes is None:
+        n = C.c_size_t()
+        rc = L.at_mjpg_dense_host(jpg, len(jpg), int(width), int(height), int(bool(keep_chroma)), None, 0,
+                                  C.byref(n))
+        if rc < 0:
+            raise MjpgError("at_mjpg_dense_host", rc)
+        nbytes = n.value
+    out = np.empty(int(nbytes), np.uint8)
+    rounds = C.c_int()
+    rc = L.at_mjpg_entropy_host(jpg, len(jpg), int(width), int(height), int(subseq_bytes), int(bool(keep_chroma)),
+                                out.ctypes.data, out.size, C.byref(rounds))
+    if rc < 0:
+        raise MjpgError("at_mjpg_entropy_host", rc)
+    return out, rounds.value
 
 
 def game_piece_preprocess_device(bgr_ptr: int, width: int, height: int, out_ptr: int, out_width: int = 640,
@@ -505,6 +552,7 @@ class GpuDetector:
         self._n = (C.c_int * self.max_batch)()
         self._last = [[] for _ in range(self.max_batch)]
         self._last_status = 0
+        self._mjpg_device_entropy = False
 
     def close(self):
         if getattr(self, "_h", None):
@@ -620,6 +668,10 @@ class GpuDetector:
         rc = load_library().at_detect_mjpg_batch(self._h, ptrs, lens, len(jpgs), self._out, self._cap, self._n,
                                                  C.byref(bad))
         self._last_status = rc
+        if rc == AT_E_INVALID and bad.value < 0 and self._mjpg_device_entropy:
+            # bad entropy-coded data, seen on the device: those frames are empty (frame_status
+            # tells which), the others' results are valid
+            return self._unpack(len(jpgs))
         if rc in (AT_E_UNSUPPORTED, AT_E_INVALID):
             raise MjpgError("at_detect_mjpg_batch", rc, bad.value if bad.value >= 0 else None)
         if rc < 0 and rc != AT_E_CAPACITY:
@@ -640,6 +692,23 @@ class GpuDetector:
         game-piece tensors).  Off by default."""
         _check(load_library().at_mjpg_set_color(self._h, int(bool(on))), "at_mjpg_set_color")
 
+    def set_mjpg_device_entropy(self, on=True):
+        """at_mjpg_set_device_entropy: from the next MJPG batch on the host only parses the
+        markers and the GPU decodes the entropy-coded data too (k_mjpg_entropy).  A frame whose
+        data turns out bad there is empty, frame_status gives AT_E_INVALID for it and
+        last_status is AT_E_INVALID; the other frames' results stand.  Off by default."""
+        _check(load_library().at_mjpg_set_device_entropy(self._h, int(bool(on))), "at_mjpg_set_device_entropy")
+        self._mjpg_device_entropy = bool(on)
+
+    def set_mjpg_subseq(self, nbytes: int):
+        """at_mjpg_set_subseq: the piece size S of the device entropy decode (16..256, a power of two)."""
+        _check(load_library().at_mjpg_set_subseq(self._h, int(nbytes)), "at_mjpg_set_subseq")
+
+    @property
+    def last_status(self):
+        """Code of the last synchronous detect call or collect (0, AT_E_CAPACITY, AT_E_INVALID)."""
+        return self._last_status
+
     def mjpg_bgr_ptr(self, frame=0):
         """at_mjpg_bgr: device pointer of frame `frame`'s BGR8 image of the last (colour-on
         MJPG) batch, valid until the next batch."""
@@ -655,7 +724,7 @@ class GpuDetector:
         return out
 
     MJPG_STATS = ("compressed_bytes", "device_bytes", "dense_frames", "host_decode_us", "idct_kernel_ns",
-                  "color_kernels_ns")
+                  "color_kernels_ns", "entropy_kernel_ns", "host_route_frames", "sync_rounds")
 
     def mjpg_stats(self):
         """at_mjpg_stats of the last MJPG batch."""
@@ -682,7 +751,8 @@ class GpuDetector:
         this detector's at_detection buffer; counts_only=True skips building Python
         objects from it and returns the per-frame counts (what a C++ caller sees)."""
         rc = load_library().at_collect(self._h, self._out, self._cap, self._n)
-        if rc < 0 and rc != AT_E_CAPACITY:
+        self._last_status = rc
+        if rc < 0 and rc != AT_E_CAPACITY and not (rc == AT_E_INVALID and self._mjpg_device_entropy and self._pending):
             _check(rc, "at_collect")
         if counts_only:
             return [self._n[f] for f in range(self._pending)]

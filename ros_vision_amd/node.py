@@ -222,7 +222,7 @@ class ApriltagsDetectorNode:
     """ApriltagsDetector (apriltags_cuda_detector.cu) without the ROS transport."""
 
     def __init__(self, width, height, parameters=None, calibration_dir=None, system_config_path=None,
-                 publishers=None, device=0, mjpg_color=False, image_jpeg=None):
+                 publishers=None, device=0, mjpg_color=False, image_jpeg=None, mjpg_device_entropy=False):
         self.params = dict(PARAMETER_DEFAULTS)
         self.params.update(parameters or {})
         serial = self.params["camera_serial"]
@@ -239,6 +239,10 @@ class ApriltagsDetectorNode:
         self.mjpg_color = bool(mjpg_color)
         if self.mjpg_color:
             self.detector.set_mjpg_color(True)
+        # "jpeg" frames: the GPU decodes the entropy-coded data too (the host parses markers only)
+        self.mjpg_device_entropy = bool(mjpg_device_entropy)
+        if self.mjpg_device_entropy:
+            self.detector.set_mjpg_device_entropy(True)
         self.publishers = publishers or {}
         self.pose_topic = self.params["publish_pose_to_topic"]
         self.camera_pose_topic = self.pose_topic + "_camera"
