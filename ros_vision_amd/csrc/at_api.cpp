@@ -458,6 +458,7 @@ int at_create(const at_config* cfg, const at_camera* cam, at_detector** out) {
   p.lblob_wg = knob("AT_LBLOB_WG") ? std::max(16, knob_int("AT_LBLOB_WG", 0)) : 0;  // experiment
   p.sblob_wg = knob("AT_SBLOB_WG") ? std::max(16, knob_int("AT_SBLOB_WG", 0)) : 0;  // experiment
   p.dec_wg = knob("AT_DEC_WG") ? std::max(16, knob_int("AT_DEC_WG", 0)) : 0;  // experiment
+  p.dec_lpq = knob_int("AT_DEC_LPQ", 0) == 64 ? 64 : 0;  // experiment (16 is the product's)
   p.fam = family_desc(*fam);
   d->use_graphs = !knob_int("AT_NO_GRAPH", 0);
   if (!(cfg->tag_size >= 0) || !std::isfinite(cfg->tag_size)) {
@@ -582,9 +583,10 @@ int at_create(const at_config* cfg, const at_camera* cam, at_detector** out) {
   b.qcand = (QuadCand*)dalloc((size_t)b.qcand_cap * sizeof(QuadCand));
   // overflow area for the peak keys of pathological large blobs (one per large-blob team)
   b.s_pk = (uint64_t*)dalloc((size_t)2 * d->nblobwg * (kSortCap / 2) * 8);  // a slot per team (<= 2 nblobwg teams)
-  // refine samples past LDS, one region per k_decode workgroup of the grid
-  // launch_pipeline uses for a full batch (decode_grid)
-  b.rsamp = (double*)dalloc((size_t)decode_grid(d->nblobwg, d->B) * 2 * (kMaxRefineSamples - kLdsRefine) * 8);
+  // refine samples past LDS, one region per k_decode workgroup (throughput mode, where
+  // launch_pipeline packs four quads into a wave: per row of a workgroup's wave) of the
+  // grid launch_pipeline uses for a full batch (decode_grid; AT_DEC_WG can only lower it)
+  b.rsamp = (double*)dalloc(decode_scratch_doubles(d->nblobwg, d->B, g.ctw == 64) * 8);
   if (oom) return fail(AT_E_NOMEM);
   if (prepare_kernels(g) != hipSuccess) return fail(AT_E_HIP);
   // frame pointer table: fine-grained mapped host memory read by k_pre directly

@@ -84,6 +84,24 @@ inline int decode_grid(int nblobwg, int B) {
   const int hi = nblobwg * kDecodeGridPerBlobWg, want = 64 * B;
   return nblobwg * 2 > (want < hi ? want : hi) ? nblobwg * 2 : (want < hi ? want : hi);
 }
+// Throughput mode packs 64 / kDecRowLanes quads into a decode wave, one per row of
+// lanes, on the same grid (16 waves per CU in flight: at 720p, 192 frames, two to
+// three groups of four quads per wave).  A quarter of the grid, as many quads in
+// flight as before, leaves a SIMD one wave: the serialized kernel 0.207 ms against
+// 0.183 one quad per wave, where the whole grid takes 0.125; concurrent throughput is
+// the same for every grid size tried (profiles/dec_rows).  A row holds its quad's first
+// kRowRefine refine samples in LDS (every quad of sides under 136 px), the rest in
+// the row's global scratch.
+constexpr int kDecRowLanes = 16;
+constexpr int kRowRefine = 64;
+// doubles of DevBufs::rsamp: a region per workgroup of the grid for one quad per wave;
+// a detector that can launch the packed waves (`packed`: throughput mode) has a region
+// per row instead (it may launch either)
+inline size_t decode_scratch_doubles(int nblobwg, int B, bool packed) {
+  const size_t one = 2 * (size_t)(kMaxRefineSamples - kLdsRefine);
+  const size_t rows = (64 / kDecRowLanes) * 2 * (size_t)(kMaxRefineSamples - kRowRefine);
+  return (size_t)decode_grid(nblobwg, B) * (packed && rows > one ? rows : one);
+}
 
 // ---- stages of one launch sequence (per-stage event timing) ----------------
 constexpr int kNumStages = 12;
@@ -167,6 +185,7 @@ struct Params {
   int lblob_wg;   // throughput-mode large-blob kernel's persistent grid (AT_LBLOB_WG; 0: nblobwg)
   int sblob_wg;   // small-blob kernel's persistent grid (AT_SBLOB_WG; 0: 2 nblobwg)
   int dec_wg;     // k_decode's persistent grid (AT_DEC_WG, experiment; 0: decode_grid)
+  int dec_lpq;    // k_decode's lanes per quad in throughput mode (AT_DEC_LPQ, experiment; 0: kDecRowLanes)
   FamilyDesc fam;
   int gp_w, gp_h, gp_c;  // game-piece preprocessing output (at_gp_enable); gp_c == 0: off
 };

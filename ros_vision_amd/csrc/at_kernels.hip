@@ -2715,6 +2715,90 @@ __device__ int homography_wave(const float (*qc)[2], double* A, double* H) {
   return 0;
 }
 
+// homography_wave for 64 / LPQ systems at once, one per row of LPQ lanes (qc, A and
+// H are the row's own): the same per-element sequence of operations and the same
+// first-strict-maximum pivot, the elimination elements of a step dealt over the
+// row's lanes (four to a lane).  `live` (uniform within a row) says whether the row has a
+// system at all; a singular one clears it; rl is the lane's rank in its row.  The whole wave reaches every barrier
+// whatever its rows decide.  Returns the row's `live`; H valid in LDS after the
+// last barrier.
+template <int LPQ>
+__device__ bool homography_rows(bool live, int rl, const float (*qc)[2], double* A, double* H) {
+  static_assert(LPQ >= 16 && 64 % LPQ == 0, "a row holds the 9 lanes of a swap and of H");
+  if (live) {
+    for (int e = rl; e < 72; e += LPQ) {
+      const int row = e / 9, col = e % 9, i = row >> 1;
+      const double c0 = (i == 0 || i == 3) ? -1 : 1, c1 = (i == 0 || i == 1) ? -1 : 1;
+      const double c2 = qc[i][0], c3 = qc[i][1];
+      const int k = (row & 1) ? col - 3 : col;
+      const double cz = (row & 1) ? c3 : c2;
+      double v = 0;
+      if (k == 0) v = c0;
+      else if (k == 1) v = c1;
+      else if (k == 2) v = 1;
+      if (col == 6) v = -c0 * cz;
+      else if (col == 7) v = -c1 * cz;
+      else if (col == 8) v = cz;
+      A[e] = v;
+    }
+  }
+  team_sync<64>();
+  for (int col = 0; col < 8; col++) {
+    double v = -1.0;
+    int row = 64;
+    if (live && rl < 8 - col) {
+      row = col + rl;
+      v = fabs(A[row * 9 + col]);
+      if (!(v > 0.0)) { v = -1.0; row = 64; }
+    }
+#pragma unroll
+    for (int d = 1; d < 8; d <<= 1) {  // (lanes 0-7 of every row)
+      const double ov = __shfl_xor(v, d);
+      const int orow = __shfl_xor(row, d);
+      if (ov > v || (ov == v && orow < row)) { v = ov; row = orow; }
+    }
+    v = __shfl(v, 0, LPQ);
+    row = __shfl(row, 0, LPQ);
+    if (!(v >= 1e-10)) live = false;  // singular (a row without a system stays so: v = -1)
+    if (live && row != col && rl <= 8 - col) {
+      const int i = col + rl;
+      const double t = A[col * 9 + i];
+      A[col * 9 + i] = A[row * 9 + i];
+      A[row * 9 + i] = t;
+    }
+    team_sync<64>();
+    // a pair of lanes per system row i (col+1..7), four of its columns col+1..8 each: one
+    // division per lane and step (dealt element by element over the row's lanes,
+    // col 0's 56 elements took four rounds with a division each)
+    if (live && (rl >> 1) < 7 - col) {
+      const int i = col + 1 + (rl >> 1);
+      const double fct = A[i * 9 + col] / A[col * 9 + col];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int j = col + 1 + 4 * (rl & 1) + q;
+        if (j <= 8) A[i * 9 + j] -= fct * A[col * 9 + j];
+      }
+    }
+    team_sync<64>();
+  }
+  double x[8];
+#pragma unroll
+  for (int col = 7; col >= 0; col--) {
+    double sum = 0;
+#pragma unroll
+    for (int i = col + 1; i < 8; i++) sum += A[col * 9 + i] * x[i];
+    x[col] = (A[col * 9 + 8] - sum) / A[col * 9 + col];
+  }
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+      if (rl == k) H[k] = x[k];
+    if (rl == 8) H[8] = 1;
+  }
+  team_sync<64>();
+  return live;
+}
+
 struct GrayModel {
   double A[3][3], B[3], C[3];
 };
@@ -4716,33 +4800,54 @@ __device__ void decode_finish(const DevBufs& b, int lane, uint32_t nq) {
 #ifndef AT_DEC_WAVES
 #define AT_DEC_WAVES 4
 #endif
-// POSE (latency mode, tag_size > 0): a second wave per workgroup estimates the
-// tag pose (k_pose's work) of every quad as soon as its homography is known,
-// while the first wave decodes the bits; the pose is computed on the unrotated
-// homography and corners and rotated with the decoded orientation afterwards
-// (R = R0 Rz(rot), t = t0: the corner correspondence of a 90-degree turn of
-// the tag frame), so the B = 1 chain is homography + pose instead of decode +
-// pose.  The last workgroup to finish hands the control block to the host.
-template <bool POSE>
-__global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_waves_per_eu(POSE ? 1 : AT_DEC_WAVES))) void k_decode(DevBufs b, Geom g, Params prm, int B, int fmt) {
+
+// ---- throughput mode: 64 / LPQ quads per wave, one per row of LPQ lanes ----------
+// Most of a quad's instructions run on 1-4 lanes (edge moments, corner intersections,
+// the pivot steps, the gray models, the scores, the record), and an instruction costs
+// the same issue cycles with one lane active as with 64.  With one quad per row those
+// run for every row at once; the full-width phases (refine, border and bit samples,
+// code match) loop over a row's tasks in strides of LPQ.  Every quad's arithmetic and
+// its order are those of the one-quad-per-wave body below (k_decode's LPQ = 64 branch),
+// restated phase by phase with the same phase numbers: a change to a phase's arithmetic
+// there has its twin here.  That halves the kernel's VALU instructions and, alone,
+// leaves its time where it was.  The A/Bs point at the refine's scattered byte loads as
+// the bound (equal time at half the instructions, -20 % with a third fewer loads; no
+// memory-pipeline counter was recorded, so this is an inference), so the refine here
+// also loads each distinct pixel once (see there), which is where its time falls
+// (profiles/dec_rows).
+//
+// A row's LDS: the areas whose lifetimes do not overlap share one union -- the refine
+// samples (phases 1-2), the DLT system (4), the gray-model samples (5-6), the cell
+// values (7-8) -- so four rows fit in what one quad's DecodeShared took.
+struct DecodeRow {
+  union {
+    struct { double sx[kRowRefine], sy[kRowRefine]; } ref;
+    double A[72];
+    struct { double x[64], y[64], v[64]; uint8_t valid[64]; } gm;
+    double values[kMaxTotalWidth * kMaxTotalWidth];
+  } u;
+  float qc[4][2];
+  int nsamp[4], samp_off[4];
+  float enx[4], eny[4];
+  double lines[4][4];
+  double H[9];
+  double wC[3], bC[3];
+  int f;          // the quad's frame and blob rank, parked here until the record
+  uint32_t rank;  // (held in registers they would be spilled across the refine loop)
+};
+
+template <int LPQ>
+__device__ __forceinline__ void decode_rows(const DevBufs& b, const Geom& g, const Params& prm, int B, int fmt) {
+  constexpr int NR = 64 / LPQ;  // rows (quads) per wave
   constexpr int RCAP = kMaxRefineSamples;
-  __shared__ DecodeShared S;
-  __shared__ PoseHandoff P;
+  constexpr int kBitRounds = kMaxFamilyBits / LPQ;
+  __shared__ DecodeRow rows[NR];
+  __shared__ uint32_t qpre[kMaxBatch + 1];
   const int tid = threadIdx.x;
+  const int row = tid / LPQ, rl = tid % LPQ;  // the lane's row and its rank within it
   kt_begin(b, 10);
-  if (POSE) {
-    if (tid == 0) { P.seq = 0; P.ack = 0; P.exit = 0; }
-    __syncthreads();
-    if (tid >= 64) {
-      pose_worker(P, prm);
-      return;
-    }
-  }
-  double* gsx = b.rsamp + (size_t)blockIdx.x * (2 * (kMaxRefineSamples - kLdsRefine));
-  double* gsy = gsx + (kMaxRefineSamples - kLdsRefine);
+  constexpr int kGy = kMaxRefineSamples - kRowRefine;  // the y samples follow the x samples
   // exclusive prefix of the per-frame candidate counts: item -> (frame, index)
-  // (all lanes load the counts at once, B <= 256 = 4 per lane; wave scan)
-  uint32_t* qpre = S.qpre;
   {
     uint32_t c[kMaxBatch / 64], sum = 0;
 #pragma unroll
@@ -4764,7 +4869,8 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
   team_sync<64>();
   const uint32_t nq = qpre[B];
 
-  // AT_PHASE_PROBE: accumulated wall-clock per phase (probe[128 + k], counts [160 + k])
+  // AT_PHASE_PROBE: accumulated wall-clock per phase of a group of NR quads
+  // (probe[128 + k], counts [160 + k])
   uint32_t pacc[21] = {0};
   uint64_t t_last = 0;
   auto phase = [&](int k) {
@@ -4777,71 +4883,94 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
       t_last = now;
     }
   };
-  // static round-robin over the queue (every entry is an accepted quad: the blob
-  // kernels append only those)
-  const uint32_t G = gridDim.x;
-  uint32_t pose_seq = 0;  // (POSE) quads handed to the pose wave
-  // the next item's queue entry (its corners on lanes 0-3) and frame address are
-  // loaded while this one is processed: an item's chain starts at its gray loads
+  // static round-robin over the queue in groups of NR consecutive entries (mostly of
+  // one frame), one per row; rows past the end of the queue idle.  The next group's
+  // entries (corners on lanes 0-3 of the row) and frame addresses are loaded before
+  // this group's code match, where few registers are live, and arrive during it.
+  // (Dequeuing the groups with one atomic each measured slower at every grid size,
+  // 0.132 against 0.125 ms: the ticket has to be back before the prefetch can start.)
   struct ItemPre {
     int f;
     uint32_t rank;
     float px, py;
     const uint8_t* gsrc;
   };
-  auto prefetch = [&](uint32_t it) -> ItemPre {
-    int lo = 0, hi = B - 1;  // last frame whose prefix <= it (the entry's frame)
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (qpre[mid] <= it) lo = mid;
-      else hi = mid - 1;
+  auto prefetch = [&](uint32_t it, int rl) -> ItemPre {
+    ItemPre p = {};
+    if (it < nq) {
+      int lo = 0, hi = B - 1;  // last frame whose prefix <= it (the entry's frame)
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (qpre[mid] <= it) lo = mid;
+        else hi = mid - 1;
+      }
+      const QuadCand* q = &b.qcand[(size_t)lo * kQuadCandPerFrame + (it - qpre[lo])];
+      p.f = lo;
+      p.rank = q->rank;
+      p.px = rl < 4 ? q->p[rl & 3][0] : 0.f;
+      p.py = rl < 4 ? q->p[rl & 3][1] : 0.f;
+      p.gsrc = fmt == 1 ? b.gray + (size_t)lo * g.W * g.H : b.frames[lo];
     }
-    const QuadCand* q = &b.qcand[(size_t)lo * kQuadCandPerFrame + (it - qpre[lo])];
-    ItemPre p;
-    p.f = lo;
-    p.rank = q->rank;
-    p.px = tid < 4 ? q->p[tid & 3][0] : 0.f;
-    p.py = tid < 4 ? q->p[tid & 3][1] : 0.f;
-    // luma of pixel i = y W + x: the frame's own Y bytes for YUYV (every second byte)
-    // and GRAY8 input, the gray plane k_pre wrote for BGR8
-    p.gsrc = fmt == 1 ? b.gray + (size_t)lo * g.W * g.H : b.frames[lo];
     return p;
   };
-  ItemPre nxt = {};
-  if (blockIdx.x < nq) nxt = prefetch(blockIdx.x);
-  for (uint32_t item = blockIdx.x; item < nq; item += G) {
+  const uint32_t G = gridDim.x;
+  const int wab = prm.fam.width_at_border, tw = prm.fam.total_width, nbits = prm.fam.nbits;
+  const int minc = (wab - tw) / 2;
+  const uint32_t gsh = fmt == 0 ? 1 : 0, wsh = (uint32_t)g.W << gsh;  // (YUYV: every second byte)
+  ItemPre nxt = prefetch(NR * blockIdx.x + row, rl);
+  for (uint32_t base = NR * blockIdx.x; base < nq; base += NR * G) {
+    // (the lane's row and rank made opaque per group, and the rank again per phase: what
+    // follows from them -- LDS addresses, tag coordinates, cell indices -- hoisted out of
+    // the item loop is spilled to scratch and reloaded, one round trip each)
+    int tq = tid;
+    __asm__ volatile("" : "+v"(tq));
+    const int rowq = tq / LPQ;
+    int rlq = tq % LPQ;
+    DecodeRow& S = rows[rowq];
+    // refine samples past the row's LDS area: one global region per row of the grid
+    // (x samples, then y samples)
+    auto gref = [&](int i) -> double* {
+      return b.rsamp + ((size_t)blockIdx.x * NR + rowq) * (2 * kGy) + (i - kRowRefine);
+    };
+    const uint32_t item = base + rowq;
     const ItemPre cur = nxt;
-    if (item + G < nq) nxt = prefetch(item + G);
-    const int f = cur.f;
-    const uint32_t qrank = cur.rank;
+    // the row decodes a quad; cleared where the one-quad body leaves the item (singular
+    // homography, hdet == 0, white model below the black one): the row then idles
+    // through the remaining phases, whose barriers the whole wave reaches
+    bool live = item < nq;
     const uint8_t* gsrc = cur.gsrc;
-    const int gsh = fmt == 0 ? 1 : 0;
-    auto pix = [&](size_t i) -> uint32_t { return gsrc[i << gsh]; };
-    if (tid < 4) { S.qc[tid][0] = cur.px; S.qc[tid][1] = cur.py; }
+    // the luma of pixel (x, y) of the row's frame: a frame's bytes fit a 32-bit offset,
+    // so a load costs one 32-bit multiply-add and the 64-bit add to the row's address
+    // (global loads: the frame pointer comes from a table, which alone would make them flat)
+    typedef const __attribute__((address_space(1))) uint8_t* gbytes;
+    auto pix = [&](int x, int y) -> uint32_t { return ((gbytes)gsrc)[(uint32_t)y * wsh + ((uint32_t)x << gsh)]; };
+    if (live && rlq < 4) { S.qc[rlq][0] = cur.px; S.qc[rlq][1] = cur.py; }
+    if (live && rlq == 0) { S.f = cur.f; S.rank = cur.rank; }
     team_sync<64>();
     phase(0);
     if (prm.refine_edges) {
-      if (tid < 4) {
-        const int a2 = tid, b2 = (tid + 1) & 3;
+      if (live && rlq < 4) {
+        const int a2 = rlq, b2 = (rlq + 1) & 3;
         float nx = S.qc[b2][1] - S.qc[a2][1];
         float ny = -S.qc[b2][0] + S.qc[a2][0];
         const float mag = sqrtf(nx * nx + ny * ny);
         nx /= mag;
         ny /= mag;
         const int nsf = (int)(mag / 8);
-        S.nsamp[tid] = nsf > 16 ? nsf : 16;
-        S.enx[tid] = nx;
-        S.eny[tid] = ny;
+        S.nsamp[rlq] = nsf > 16 ? nsf : 16;
+        S.enx[rlq] = nx;
+        S.eny[rlq] = ny;
       }
       team_sync<64>();
-      if (tid == 0) {
+      if (live && rlq == 0) {
         int acc = 0;
         for (int k = 0; k < 4; k++) { S.samp_off[k] = acc; acc += S.nsamp[k]; }
       }
       team_sync<64>();
-      const int total = min(S.samp_off[3] + S.nsamp[3], RCAP);
-      if (tid == 0 && S.samp_off[3] + S.nsamp[3] > RCAP) atomicOr(b.status + f, kStatusQuadsOverflow);
-      for (int t = tid; t < total; t += kDecodeThreads) {
+      const int want = live ? S.samp_off[3] + S.nsamp[3] : 0;
+      const int total = min(want, RCAP);
+      if (rlq == 0 && want > RCAP) atomicOr(b.status + S.f, kStatusQuadsOverflow);
+      for (int t = rlq; t < total; t += LPQ) {  // (a row's trip count follows its own quad)
         int edge = 0;
         while (edge < 3 && t >= S.samp_off[edge + 1]) edge++;
         const int s = t - S.samp_off[edge];
@@ -4851,31 +4980,37 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
         const double alpha = (1.0 + s) / (nsamples + 1);
         const double x0 = alpha * S.qc[a2][0] + (1 - alpha) * S.qc[b2][0];
         const double y0 = alpha * S.qc[a2][1] + (1 - alpha) * S.qc[b2][1];
-        // the 25 steps n = -3, -2.75, ..., 3 (exact in double): every gray load is
-        // issued before the first is consumed, then the sums run in step order
-        constexpr int kSteps = 25;
-        int g1v[kSteps], g2v[kSteps];
+        // the 25 steps n = -3, -2.75, ..., 3 compare the pixels at n + 1 and n - 1 along
+        // the normal.  n + 1 of step k is n - 1 of step k + 8 (both exact in double), so
+        // the 50 samples are 33 positions, at m = -4, -3.75, ..., 4, a quarter of a pixel
+        // apart: a position that falls into the pixel of the one before it takes its
+        // value, the others are loaded, each once (-1 outside the image).  By the A/Bs the
+        // kernel's time follows these scattered byte loads (a cache line per lane and
+        // load), not its arithmetic.  Every load is issued before the first is consumed,
+        // then the sums run in step order.
+        constexpr int kSteps = 25, kPos = kSteps + 8;
+        int pv[kPos];
+        int xp = 0, yp = 0;
 #pragma unroll
-        for (int k = 0; k < kSteps; k++) {
-          const double nn = -3.0 + 0.25 * k;
-          const int x1 = (int)(x0 + (nn + 1) * nx);
-          const int y1 = (int)(y0 + (nn + 1) * ny);
-          const int x2 = (int)(x0 + (nn - 1) * nx);
-          const int y2 = (int)(y0 + (nn - 1) * ny);
-          const bool in = !(x1 < 0 || x1 >= g.W || y1 < 0 || y1 >= g.H) && !(x2 < 0 || x2 >= g.W || y2 < 0 || y2 >= g.H);
-          g1v[k] = -1;
-          g2v[k] = 0;
-          if (in) {
-            g1v[k] = (int)pix((size_t)y1 * g.W + x1);
-            g2v[k] = (int)pix((size_t)y2 * g.W + x2);
-          }
+        for (int j = 0; j < kPos; j++) {
+          const double m = -4.0 + 0.25 * j;
+          const int x = (int)(x0 + m * nx);
+          const int y = (int)(y0 + m * ny);
+          const bool same = j > 0 && x == xp && y == yp;
+          pv[j] = same ? -2 : -1;
+          if (!same && !(x < 0 || x >= g.W || y < 0 || y >= g.H)) pv[j] = (int)pix(x, y);
+          xp = x;
+          yp = y;
         }
+#pragma unroll
+        for (int j = 1; j < kPos; j++)
+          if (pv[j] == -2) pv[j] = pv[j - 1];
         double Mn = 0, Mcount = 0;
 #pragma unroll
         for (int k = 0; k < kSteps; k++) {
           const double nn = -3.0 + 0.25 * k;
-          const int g1 = g1v[k], g2 = g2v[k];
-          if (g1 < g2) continue;  // also skips out-of-image steps (g1 = -1)
+          const int g1 = pv[k + 8], g2 = pv[k];
+          if (g1 < 0 || g2 < 0 || g1 < g2) continue;  // (a step with a pixel outside the image is skipped)
           const double weight = (double)((g2 - g1) * (g2 - g1));
           Mn += weight * nn;
           Mcount += weight;
@@ -4887,22 +5022,21 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
           by = y0 + n0 * ny;
           undistort(prm, &bx, &by);
         }
-        if (t < kLdsRefine) {
-          S.sx[t] = bx;
-          S.sy[t] = by;
+        if (t < kRowRefine) {
+          S.u.ref.sx[t] = bx;
+          S.u.ref.sy[t] = by;
         } else {
-          gsx[t - kLdsRefine] = bx;
-          gsy[t - kLdsRefine] = by;
+          gref(t)[0] = bx;
+          gref(t)[kGy] = by;
         }
       }
       team_sync<64>();
       phase(1);
-      // per edge (lane e), the moments in the reference's sample order; samples are
-      // staged 8 at a time in registers so their LDS reads overlap
-      if (tid < 4) {
+      // per edge (lane e of the row), the moments in the reference's sample order
+      if (live && rlq < 4) {
         double Mx = 0, My = 0, Mxx = 0, Mxy = 0, Myy = 0, N = 0;
-        const int o = S.samp_off[tid];
-        const int ns = min(S.nsamp[tid], RCAP - o);
+        const int o = S.samp_off[rlq];
+        const int ns = min(S.nsamp[rlq], RCAP - o);
         for (int c = 0; c < ns; c += 8) {
           double xs[8], ys[8];
 #pragma unroll
@@ -4911,8 +5045,8 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
             xs[k] = __longlong_as_double(0x7ff8deadbeef0000ll);
             ys[k] = 0;
             if (c + k < ns) {
-              xs[k] = i < kLdsRefine ? S.sx[i] : gsx[i - kLdsRefine];
-              ys[k] = i < kLdsRefine ? S.sy[i] : gsy[i - kLdsRefine];
+              xs[k] = i < kRowRefine ? S.u.ref.sx[i] : gref(i)[0];
+              ys[k] = i < kRowRefine ? S.u.ref.sy[i] : gref(i)[kGy];
             }
           }
 #pragma unroll
@@ -4925,14 +5059,14 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
         const double Ex = Mx / N, Ey = My / N;
         const double Cxx = Mxx / N - Ex * Ex, Cxy = Mxy / N - Ex * Ey, Cyy = Myy / N - Ey * Ey;
         const double nt = .5 * (double)det_atan2f_call((float)(-2 * Cxy), (float)(Cyy - Cxx));
-        S.lines[tid][0] = Ex;
-        S.lines[tid][1] = Ey;
-        S.lines[tid][2] = (double)det_cosf((float)nt);
-        S.lines[tid][3] = (double)det_sinf((float)nt);
+        S.lines[rlq][0] = Ex;
+        S.lines[rlq][1] = Ey;
+        S.lines[rlq][2] = (double)det_cosf((float)nt);
+        S.lines[rlq][3] = (double)det_sinf((float)nt);
       }
       team_sync<64>();
       phase(2);
-      if (tid == 0) {
+      if (live && rlq == 0) {
         float qp[4][2];
         for (int k = 0; k < 4; k++) { qp[k][0] = S.qc[k][0]; qp[k][1] = S.qc[k][1]; }
         for (int i = 0; i < 4; i++) {
@@ -4956,205 +5090,210 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
       team_sync<64>();
       phase(3);
     }
-    if (AT_DIAG_STOP(prm, 6)) continue;
+    if (AT_DIAG_STOP(prm, 6)) {  // (uniform)
+      nxt = prefetch(item + NR * G, rlq);
+      continue;
+    }
     // ---- homography (quad_update_homographies / homography_compute2) -----------
-    if (homography_wave(S.qc, S.A, S.H) != 0) continue;
-    if (tid == 0) {
-      const double* H = S.H;
-      const double hdet = H[0] * (H[4] * H[8] - H[5] * H[7]) - H[1] * (H[3] * H[8] - H[5] * H[6]) +
-                          H[2] * (H[3] * H[7] - H[4] * H[6]);
-      S.ok = hdet != 0;
-    }
-    team_sync<64>();
-    phase(4);
-    if (!S.ok) continue;
-    uint32_t seq = 0;
-    if (POSE) {  // hand the homography and the unrotated corners to the pose wave
-      if (tid < 9) P.H[tid] = S.H[tid];
-      if (tid < 4) {
-        const int tcx = (tid == 1 || tid == 2) ? 1 : -1, tcy = tid < 2 ? 1 : -1;
-        hproject(S.H, tcx, tcy, &P.p[tid][0], &P.p[tid][1]);
-      }
-      seq = ++pose_seq;
-      team_sync<64>();
-      if (tid == 0) __hip_atomic_store(&P.seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    uint32_t bc = 0xffffffffu;
-    double margin_d = -1;
-    do {
-    // ---- quad_decode: border gray models (8 patterns x width_at_border <= 8
-    // samples: lane = 8 * pattern + sample) ----
-    const int wab = prm.fam.width_at_border, tw = prm.fam.total_width, nbits = prm.fam.nbits;
-    const int minc = (wab - tw) / 2;
+    live = homography_rows<LPQ>(live, rlq, S.qc, S.u.A, S.H);
     {
-      const int pidx = tid >> 3, i = tid & 7;
-      float p0, p1, p2, p3;
-      border_pattern(pidx, (float)wab, p0, p1, p2, p3);
-      const double tagx01 = (double)((p0 + (float)i * p2) / (float)wab);
-      const double tagy01 = (double)((p1 + (float)i * p3) / (float)wab);
-      const double tagx = 2 * (tagx01 - 0.5), tagy = 2 * (tagy01 - 0.5);
-      double px, py;
-      hproject(S.H, tagx, tagy, &px, &py);
-      const int ix = (int)px, iy = (int)py;
-      S.gmx[tid] = tagx;
-      S.gmy[tid] = tagy;
-      S.gmvalid[tid] = i < wab && !(ix < 0 || iy < 0 || ix >= g.W || iy >= g.H);
-      S.gmv[tid] = S.gmvalid[tid] ? (double)pix((size_t)iy * g.W + ix) : 0.0;
+      int ok = 0;
+      if (live && rlq == 0) {
+        const double* H = S.H;
+        const double hdet = H[0] * (H[4] * H[8] - H[5] * H[7]) - H[1] * (H[3] * H[8] - H[5] * H[6]) +
+                            H[2] * (H[3] * H[7] - H[4] * H[6]);
+        ok = hdet != 0;
+      }
+      live = __shfl(ok, 0, LPQ) != 0;
     }
-    for (int t = tid; t < tw * tw; t += kDecodeThreads) S.values[t] = 0;
+    phase(4);
+    // ---- quad_decode: border gray models (8 patterns x width_at_border <= 8
+    // samples: task t = 8 * pattern + sample, LPQ of them per round) ----
+    __asm__ volatile("" : "+v"(rlq));
+    if (live) {
+#pragma unroll 1
+      for (int r = 0; r < 64 / LPQ; r++) {
+        const int t = rlq + LPQ * r;
+        const int pidx = t >> 3, i = t & 7;
+        float p0, p1, p2, p3;
+        border_pattern(pidx, (float)wab, p0, p1, p2, p3);
+        const double tagx01 = (double)((p0 + (float)i * p2) / (float)wab);
+        const double tagy01 = (double)((p1 + (float)i * p3) / (float)wab);
+        const double tagx = 2 * (tagx01 - 0.5), tagy = 2 * (tagy01 - 0.5);
+        double px, py;
+        hproject(S.H, tagx, tagy, &px, &py);
+        const int ix = (int)px, iy = (int)py;
+        const bool valid = i < wab && !(ix < 0 || iy < 0 || ix >= g.W || iy >= g.H);
+        S.u.gm.x[t] = tagx;
+        S.u.gm.y[t] = tagy;
+        S.u.gm.valid[t] = valid;
+        S.u.gm.v[t] = valid ? (double)pix(ix, iy) : 0.0;
+      }
+    }
     team_sync<64>();
     phase(5);
-    // lane 0 builds and solves the white model, lane 1 the black one, each over
-    // its 32 samples in the serial order, eight samples staged in registers at a time
+    // lane 0 of the row builds and solves the white model, lane 1 the black one, each
+    // over its 32 samples in the serial order, eight samples staged in registers at a time
     double interp00 = 0;
-    if (tid < 2) {
+    if (live && rlq < 2) {
       GrayModel m;
       for (int k = 0; k < 3; k++) {
         m.B[k] = 0;
         for (int j = 0; j < 3; j++) m.A[k][j] = 0;
       }
       for (int grp = 0; grp < 4; grp++) {
-        const int t0 = 16 * grp + 8 * tid;
+        const int t0 = 16 * grp + 8 * rlq;
         double xs[8], ys[8], vs[8];
         int ok[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-          xs[i] = S.gmx[t0 + i];
-          ys[i] = S.gmy[t0 + i];
-          vs[i] = S.gmv[t0 + i];
-          ok[i] = S.gmvalid[t0 + i];
+          xs[i] = S.u.gm.x[t0 + i];
+          ys[i] = S.u.gm.y[t0 + i];
+          vs[i] = S.u.gm.v[t0 + i];
+          ok[i] = S.u.gm.valid[t0 + i];
         }
 #pragma unroll
         for (int i = 0; i < 8; i++)
           if (ok[i]) gm_add(m, xs[i], ys[i], vs[i]);
       }
       gm_solve(m);
-      double* C = tid == 0 ? S.wC : S.bC;
+      double* C = rlq == 0 ? S.wC : S.bC;
       for (int k = 0; k < 3; k++) C[k] = m.C[k];
       interp00 = gm_interp(m, 0, 0);
     }
-    const double w00 = __shfl(interp00, 0), b00 = __shfl(interp00, 1);
-    team_sync<64>();
-    if (w00 - b00 < 0) break;  // uniform
+    {
+      const double w00 = __shfl(interp00, 0, LPQ), b00 = __shfl(interp00, 1, LPQ);
+      if (w00 - b00 < 0) live = false;
+    }
+    team_sync<64>();  // (the gray-model samples are read: the cell values take their place)
     phase(6);
-    if (tid < nbits) {
-      const int bity = prm.fam.bity[tid], bitx = prm.fam.bitx[tid];
-      const double tagx01 = (bitx + 0.5) / wab, tagy01 = (bity + 0.5) / wab;
-      const double tagx = 2 * (tagx01 - 0.5), tagy = 2 * (tagy01 - 0.5);
-      double px, py;
-      hproject(S.H, tagx, tagy, &px, &py);
-      const int x1 = (int)floor(px - 0.5), x2 = (int)ceil(px - 0.5);
-      const double xx = px - 0.5 - x1;
-      const int y1 = (int)floor(py - 0.5), y2 = (int)ceil(py - 0.5);
-      const double yy = py - 0.5 - y1;
-      if (!(x1 < 0 || x2 >= g.W || y1 < 0 || y2 >= g.H)) {  // value_for_pixel
-        const double v = (int)pix((size_t)y1 * g.W + x1) * (1 - xx) * (1 - yy) + (int)pix((size_t)y1 * g.W + x2) * xx * (1 - yy) +
-                         (int)pix((size_t)y2 * g.W + x1) * (1 - xx) * yy + (int)pix((size_t)y2 * g.W + x2) * xx * yy;
-        const double bth = S.bC[0] * tagx + S.bC[1] * tagy + S.bC[2];
-        const double wth = S.wC[0] * tagx + S.wC[1] * tagy + S.wC[2];
-        S.values[tw * (bity - minc) + bitx - minc] = v - (bth + wth) / 2.0;
+    if (live)
+      for (int t = rlq; t < tw * tw; t += LPQ) S.u.values[t] = 0;
+    team_sync<64>();
+    __asm__ volatile("" : "+v"(rlq));
+#pragma unroll 1
+    for (int r = 0; r * LPQ < nbits; r++) {
+      const int bi = rlq + LPQ * r;
+      if (live && bi < nbits) {
+        const int bity = prm.fam.bity[bi], bitx = prm.fam.bitx[bi];
+        const double tagx01 = (bitx + 0.5) / wab, tagy01 = (bity + 0.5) / wab;
+        const double tagx = 2 * (tagx01 - 0.5), tagy = 2 * (tagy01 - 0.5);
+        double px, py;
+        hproject(S.H, tagx, tagy, &px, &py);
+        const int x1 = (int)floor(px - 0.5), x2 = (int)ceil(px - 0.5);
+        const double xx = px - 0.5 - x1;
+        const int y1 = (int)floor(py - 0.5), y2 = (int)ceil(py - 0.5);
+        const double yy = py - 0.5 - y1;
+        if (!(x1 < 0 || x2 >= g.W || y1 < 0 || y2 >= g.H)) {  // value_for_pixel
+          const double v = (int)pix(x1, y1) * (1 - xx) * (1 - yy) + (int)pix(x2, y1) * xx * (1 - yy) +
+                           (int)pix(x1, y2) * (1 - xx) * yy + (int)pix(x2, y2) * xx * yy;
+          const double bth = S.bC[0] * tagx + S.bC[1] * tagy + S.bC[2];
+          const double wth = S.wC[0] * tagx + S.wC[1] * tagy + S.wC[2];
+          S.u.values[tw * (bity - minc) + bitx - minc] = v - (bth + wth) / 2.0;
+        }
       }
     }
     team_sync<64>();
     phase(7);
-    // sharpen (apriltag.c) over the total_width^2 grid: each lane owns cells t, t+64, t+128
-    constexpr int kShR = (kMaxTotalWidth * kMaxTotalWidth + kDecodeThreads - 1) / kDecodeThreads;
-    double shv[kShR];
-    // (the lane's cell indices recomputed per quad: hoisted out of the item loop they
-    // were spilled to scratch and reloaded here, one round trip each)
-    int tl = tid;
-    __asm__ volatile("" : "+v"(tl));
+    // sharpen (apriltag.c), at the data-bit cells only: a sharpened cell depends on the
+    // unsharpened grid alone, and only the data bits' cells are read afterwards.  The
+    // kernel {0,-1,0; -1,4,-1; 0,-1,0} in the reference's tap order, its zero taps left
+    // out (see the one-quad body).  Lane i of the row holds bits i, i + LPQ, ...
+    double bitv[kBitRounds];
+    uint64_t white_bits = 0;  // bit i: data bit i (MSB first in the word)
+    __asm__ volatile("" : "+v"(rlq));
 #pragma unroll
-    for (int r = 0; r < kShR; r++) {
-      const int t = tl + 64 * r;
-      shv[r] = 0;
-      if (t < tw * tw) {
-        // the kernel {0,-1,0; -1,4,-1; 0,-1,0} in the reference's tap order, its zero taps
-        // left out: they add +-0, which changes no nonzero partial sum, and the sign of a
-        // zero sum reaches no decision (a value is never -0: v - m is +0 when v == m).
-        // The five reads are issued together (the 3x3 loop's reads went one at a time,
-        // their addresses spilled to scratch)
+    for (int r = 0; r < kBitRounds; r++) {
+      const int bi = rlq + LPQ * r;
+      bitv[r] = 0;
+      if (live && bi < nbits) {
+        const int t = tw * (prm.fam.bity[bi] - minc) + prm.fam.bitx[bi] - minc;
         const int y = t / tw, x = t % tw;
-        const double up = S.values[y > 0 ? t - tw : t], left = S.values[x > 0 ? t - 1 : t], c = S.values[t];
-        const double right = S.values[x < tw - 1 ? t + 1 : t], down = S.values[y < tw - 1 ? t + tw : t];
+        const double up = S.u.values[y > 0 ? t - tw : t], left = S.u.values[x > 0 ? t - 1 : t], c = S.u.values[t];
+        const double right = S.u.values[x < tw - 1 ? t + 1 : t], down = S.u.values[y < tw - 1 ? t + tw : t];
         double acc = 0;
         if (y > 0) acc = acc - up;
         if (x > 0) acc = acc - left;
         acc = acc + c * 4;
         if (x < tw - 1) acc = acc - right;
         if (y < tw - 1) acc = acc - down;
-        shv[r] = acc;
+        bitv[r] = c + prm.decode_sharpening * acc;
       }
+      const uint64_t m = __ballot(live && bi < nbits && bitv[r] > 0);
+      white_bits |= ((m >> (rowq * LPQ)) & ((1ull << LPQ) - 1)) << (LPQ * r);
     }
+    const uint64_t rcode0 = __builtin_bitreverse64(white_bits) >> (64 - nbits);
+    // the scores run in bit order on every lane of the row, over the row's sharpened
+    // values (handed over through the cell area, which every lane has read by now)
     team_sync<64>();
 #pragma unroll
-    for (int r = 0; r < kShR; r++) {
-      const int t = tid + 64 * r;
-      if (t < tw * tw) S.values[t] = S.values[t] + prm.decode_sharpening * shv[r];
+    for (int r = 0; r < kBitRounds; r++) {
+      const int bi = rlq + LPQ * r;
+      if (live && bi < nbits) S.u.values[bi] = bitv[r];
     }
     team_sync<64>();
-    // code word and scores: lane i reads bit i's value, the scores run in bit
-    // order on every lane (uniform v_readlane loop), the word comes from a ballot
-    double bitv = 0;
-    if (tid < nbits) bitv = S.values[tw * (prm.fam.bity[tid] - minc) + prm.fam.bitx[tid] - minc];
-    const uint64_t white_bits = __ballot(tid < nbits && bitv > 0);  // bit i: data bit i (MSB first in the word)
-    const uint64_t rcode0 = __builtin_bitreverse64(white_bits) >> (64 - nbits);
+    double margin_d = -1;
     {
       float black_score = 0, white_score = 0, black_cnt = 1, white_cnt = 1;
       for (int i = 0; i < nbits; i++) {
-        const double v = readlane_f64(bitv, i);
+        const double v = S.u.values[i];
         if (v > 0) { white_score = (float)(white_score + v); white_cnt++; }
         else { black_score = (float)(black_score - v); black_cnt++; }
       }
       margin_d = fmin((double)(white_score / white_cnt), (double)(black_score / black_cnt));
     }
     phase(8);
-    // quick_decode_codeword: first rotation, then entry, within hamming <= 2
-    // (codes are >= 5 apart, so at most one entry matches a rotation)
+    // quick_decode_codeword: first rotation, then entry, within hamming <= 2.  Every
+    // lane loads its codebook entries once and matches them against the words of all
+    // NR rows (uniform values), then a wave-wide minimum per row.
+    uint32_t bc = 0xffffffffu;
+    nxt = prefetch(item + NR * G, rlq);
     {
-      uint64_t r[4];
-      r[0] = rcode0;
+      uint64_t rc[NR][4];
+      uint32_t bcr[NR];
 #pragma unroll
-      for (int k = 1; k < 4; k++) r[k] = rotate90_n(r[k - 1], nbits);
-      // the codebook straight from HBM (L2-resident: every workgroup reads the same
-      // table; an LDS copy cost 8 KB per one-wave workgroup, and the LDS freed lets
-      // the concurrent batches' kernels co-reside: +2.8 % throughput, profiles/r03l),
-      // ten of a lane's entries loaded together (tag36h11: one round trip instead of 10)
+      for (int j = 0; j < NR; j++) {
+        rc[j][0] = wave_read(rcode0, j * LPQ);
+#pragma unroll
+        for (int k = 1; k < 4; k++) rc[j][k] = rotate90_n(rc[j][k - 1], nbits);
+        bcr[j] = 0xffffffffu;
+      }
       constexpr int kBookChunk = 10;  // (every family in one round trip: ncodes <= 640)
       for (int e0 = 0; e0 < prm.fam.ncodes; e0 += kBookChunk * kDecodeThreads) {
         uint64_t cw[kBookChunk];
 #pragma unroll
         for (int k = 0; k < kBookChunk; k++) {
-          const int ent = e0 + tid + kDecodeThreads * k;
+          const int ent = e0 + tq + kDecodeThreads * k;
           cw[k] = ent < prm.fam.ncodes ? b.book_code[ent] : 0ull;
         }
 #pragma unroll
         for (int k = 0; k < kBookChunk; k++) {
-          const int ent = e0 + tid + kDecodeThreads * k;
+          const int ent = e0 + tq + kDecodeThreads * k;
 #pragma unroll
-          for (int rot = 0; rot < 4; rot++) {
-            const int hd = __popcll(r[rot] ^ cw[k]);
-            if (ent < prm.fam.ncodes && hd <= 2) bc = min(bc, (uint32_t)((rot << 24) | (hd << 16) | ent));
-          }
+          for (int j = 0; j < NR; j++)
+#pragma unroll
+            for (int rot = 0; rot < 4; rot++) {
+              const int hd = __popcll(rc[j][rot] ^ cw[k]);
+              if (ent < prm.fam.ncodes && hd <= 2) bcr[j] = min(bcr[j], (uint32_t)((rot << 24) | (hd << 16) | ent));
+            }
         }
       }
 #pragma unroll
-      for (int d = 32; d > 0; d >>= 1) bc = min(bc, (uint32_t)__shfl_xor(bc, d));
+      for (int j = 0; j < NR; j++) {
+        const uint32_t m = wave_reduce(bcr[j], MinOp());
+        if (rowq == j) bc = m;
+      }
     }
-    } while (false);
-    if (POSE) {  // the pose of this quad is done before the next one is handed over
-      while (__hip_atomic_load(&P.ack, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seq)
-        __builtin_amdgcn_s_sleep(1);
-    }
-    if (tid == 0) {
+    if (live && rlq == 0) {
       const float margin = (float)margin_d;
       if (margin >= 0 && bc != 0xffffffffu) {
         const int rot = bc >> 24, hd = (bc >> 16) & 0xff, ent = bc & 0xffff;
+        const int f = S.f;
         DevDetection d;
         d.id = b.book_id[ent];
         d.hamming = hd;
         d.decision_margin = margin;
-        d.blob_rank = (int32_t)qrank;
+        d.blob_rank = (int32_t)S.rank;
         const double R[9] = {c_rot_c[rot], -c_rot_s[rot], 0, c_rot_s[rot], c_rot_c[rot], 0, 0, 0, 1};
         for (int i = 0; i < 3; i++)
           for (int j = 0; j < 3; j++) {
@@ -5169,26 +5308,14 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
           hproject(d.H, tcx, tcy, &d.p[i][0], &d.p[i][1]);
         }
         d.frame = (uint16_t)f;
-        if (POSE) {
-          // R = R0 Rz(rot) with the exact quarter turn, t = t0
-          const int c = rot == 0 ? 1 : rot == 2 ? -1 : 0, sn = rot == 1 ? 1 : rot == 3 ? -1 : 0;
-          for (int i = 0; i < 3; i++) {
-            d.pose_R[i * 3 + 0] = P.R[i * 3 + 0] * c + P.R[i * 3 + 1] * sn;
-            d.pose_R[i * 3 + 1] = -P.R[i * 3 + 0] * sn + P.R[i * 3 + 1] * c;
-            d.pose_R[i * 3 + 2] = P.R[i * 3 + 2];
-          }
-          for (int k = 0; k < 3; k++) d.pose_t[k] = P.t[k];
-          d.pose_err[0] = P.err[0];
-          d.pose_err[1] = P.err[1];
-        }
         // the frame's own slot; the first kDetPoolPerFrame also to the host mirror
-        // (POSE: complete; else the pose fields follow from k_pose)
+        // (the pose fields follow from k_pose)
         const uint32_t k = atomicAdd(b.ndets + f, 1u);
         if (k < (uint32_t)kMaxDets) {
           const uint32_t slot = (uint32_t)f * kMaxDets + k;
           b.dets[slot] = d;
           if (k < (uint32_t)kDetPoolPerFrame) b.hdets[(uint32_t)f * kDetPoolPerFrame + k] = d;
-          if (!POSE) b.det_work[atomicAdd(b.det_head, 1u)] = slot;
+          b.det_work[atomicAdd(b.det_head, 1u)] = slot;
         } else {
           atomicOr(b.status + f, kStatusDetsOverflow);  // (more candidates than quads: unreachable)
         }
@@ -5199,9 +5326,508 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
   }
   probe_flush(b, prm, pacc, 128, tid == 0);
   if (tid == 0) kt_end(b, 10);
-  if (POSE) {
-    if (tid == 0) __hip_atomic_store(&P.exit, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    decode_finish(b, tid, nq);
+}
+// POSE (latency mode, tag_size > 0): a second wave per workgroup estimates the
+// tag pose (k_pose's work) of every quad as soon as its homography is known,
+// while the first wave decodes the bits; the pose is computed on the unrotated
+// homography and corners and rotated with the decoded orientation afterwards
+// (R = R0 Rz(rot), t = t0: the corner correspondence of a 90-degree turn of
+// the tag frame), so the B = 1 chain is homography + pose instead of decode +
+// pose.  The last workgroup to finish hands the control block to the host.
+// LPQ, lanes per quad: 64 is the one-quad-per-wave body in the else branch below
+// (latency mode, with or without the pose wave), and the reference that decode_rows
+// above restates phase by phase: refine, moments, corners, homography, gray models, bit
+// samples, sharpen, scores, code match, record.  A change to the arithmetic of a phase
+// here has its twin there (tests/test_decode_rows.py and the throughput cases of
+// tests/test_decode_parity.py hold the packed body to the oracle, the latency cases this
+// one).  kDecRowLanes packs 64 / LPQ quads into a wave (decode_rows, throughput mode).
+// Each instantiation holds the LDS of its own branch only.  (The one-quad body stays in
+// the kernel itself: called as a function of its own it compiled to 80 spilled VGPRs
+// instead of 2.)
+template <bool POSE, int LPQ = 64>
+__global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_waves_per_eu(POSE ? 1 : AT_DEC_WAVES))) void k_decode(DevBufs b, Geom g, Params prm, int B, int fmt) {
+  if constexpr (LPQ < 64) {
+    static_assert(!POSE, "the pose wave goes with one quad per wave");
+    decode_rows<LPQ>(b, g, prm, B, fmt);
+  } else {
+    constexpr int RCAP = kMaxRefineSamples;
+    __shared__ DecodeShared S;
+    __shared__ PoseHandoff P;
+    const int tid = threadIdx.x;
+    kt_begin(b, 10);
+    if (POSE) {
+      if (tid == 0) { P.seq = 0; P.ack = 0; P.exit = 0; }
+      __syncthreads();
+      if (tid >= 64) {
+        pose_worker(P, prm);
+        return;
+      }
+    }
+    double* gsx = b.rsamp + (size_t)blockIdx.x * (2 * (kMaxRefineSamples - kLdsRefine));
+    double* gsy = gsx + (kMaxRefineSamples - kLdsRefine);
+    // exclusive prefix of the per-frame candidate counts: item -> (frame, index)
+    // (all lanes load the counts at once, B <= 256 = 4 per lane; wave scan)
+    uint32_t* qpre = S.qpre;
+    {
+      uint32_t c[kMaxBatch / 64], sum = 0;
+#pragma unroll
+      for (int k = 0; k < kMaxBatch / 64; k++) {
+        const int f = tid * (kMaxBatch / 64) + k;
+        c[k] = f < B ? min(b.nqcand[(size_t)f * kQcStride], (uint32_t)kQuadCandPerFrame) : 0u;
+        sum += c[k];
+      }
+      const uint32_t incl = wave_incl_scan(sum, AddOp(), 0u);
+      uint32_t acc = incl - sum;
+#pragma unroll
+      for (int k = 0; k < kMaxBatch / 64; k++) {
+        const int f = tid * (kMaxBatch / 64) + k;
+        if (f < B) qpre[f] = acc;
+        acc += c[k];
+      }
+      if (tid == 63) qpre[B] = incl;
+    }
+    team_sync<64>();
+    const uint32_t nq = qpre[B];
+
+    // AT_PHASE_PROBE: accumulated wall-clock per phase (probe[128 + k], counts [160 + k])
+    uint32_t pacc[21] = {0};
+    uint64_t t_last = 0;
+    auto phase = [&](int k) {
+      if (AT_PROBE_ON(prm) && tid == 0) {
+        const uint64_t now = wall_clock64();
+        if (k > 0) {
+          pacc[k] += (uint32_t)(now - t_last);
+          pacc[10 + k] += 1;
+        }
+        t_last = now;
+      }
+    };
+    // static round-robin over the queue (every entry is an accepted quad: the blob
+    // kernels append only those)
+    const uint32_t G = gridDim.x;
+    uint32_t pose_seq = 0;  // (POSE) quads handed to the pose wave
+    // the next item's queue entry (its corners on lanes 0-3) and frame address are
+    // loaded while this one is processed: an item's chain starts at its gray loads
+    struct ItemPre {
+      int f;
+      uint32_t rank;
+      float px, py;
+      const uint8_t* gsrc;
+    };
+    auto prefetch = [&](uint32_t it) -> ItemPre {
+      int lo = 0, hi = B - 1;  // last frame whose prefix <= it (the entry's frame)
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (qpre[mid] <= it) lo = mid;
+        else hi = mid - 1;
+      }
+      const QuadCand* q = &b.qcand[(size_t)lo * kQuadCandPerFrame + (it - qpre[lo])];
+      ItemPre p;
+      p.f = lo;
+      p.rank = q->rank;
+      p.px = tid < 4 ? q->p[tid & 3][0] : 0.f;
+      p.py = tid < 4 ? q->p[tid & 3][1] : 0.f;
+      // luma of pixel i = y W + x: the frame's own Y bytes for YUYV (every second byte)
+      // and GRAY8 input, the gray plane k_pre wrote for BGR8
+      p.gsrc = fmt == 1 ? b.gray + (size_t)lo * g.W * g.H : b.frames[lo];
+      return p;
+    };
+    ItemPre nxt = {};
+    if (blockIdx.x < nq) nxt = prefetch(blockIdx.x);
+    for (uint32_t item = blockIdx.x; item < nq; item += G) {
+      const ItemPre cur = nxt;
+      if (item + G < nq) nxt = prefetch(item + G);
+      const int f = cur.f;
+      const uint32_t qrank = cur.rank;
+      const uint8_t* gsrc = cur.gsrc;
+      const int gsh = fmt == 0 ? 1 : 0;
+      auto pix = [&](size_t i) -> uint32_t { return gsrc[i << gsh]; };
+      if (tid < 4) { S.qc[tid][0] = cur.px; S.qc[tid][1] = cur.py; }
+      team_sync<64>();
+      phase(0);
+      if (prm.refine_edges) {
+        if (tid < 4) {
+          const int a2 = tid, b2 = (tid + 1) & 3;
+          float nx = S.qc[b2][1] - S.qc[a2][1];
+          float ny = -S.qc[b2][0] + S.qc[a2][0];
+          const float mag = sqrtf(nx * nx + ny * ny);
+          nx /= mag;
+          ny /= mag;
+          const int nsf = (int)(mag / 8);
+          S.nsamp[tid] = nsf > 16 ? nsf : 16;
+          S.enx[tid] = nx;
+          S.eny[tid] = ny;
+        }
+        team_sync<64>();
+        if (tid == 0) {
+          int acc = 0;
+          for (int k = 0; k < 4; k++) { S.samp_off[k] = acc; acc += S.nsamp[k]; }
+        }
+        team_sync<64>();
+        const int total = min(S.samp_off[3] + S.nsamp[3], RCAP);
+        if (tid == 0 && S.samp_off[3] + S.nsamp[3] > RCAP) atomicOr(b.status + f, kStatusQuadsOverflow);
+        for (int t = tid; t < total; t += kDecodeThreads) {
+          int edge = 0;
+          while (edge < 3 && t >= S.samp_off[edge + 1]) edge++;
+          const int s = t - S.samp_off[edge];
+          const int a2 = edge, b2 = (edge + 1) & 3;
+          const int nsamples = S.nsamp[edge];
+          const float nx = S.enx[edge], ny = S.eny[edge];
+          const double alpha = (1.0 + s) / (nsamples + 1);
+          const double x0 = alpha * S.qc[a2][0] + (1 - alpha) * S.qc[b2][0];
+          const double y0 = alpha * S.qc[a2][1] + (1 - alpha) * S.qc[b2][1];
+          // the 25 steps n = -3, -2.75, ..., 3 (exact in double): every gray load is
+          // issued before the first is consumed, then the sums run in step order
+          constexpr int kSteps = 25;
+          int g1v[kSteps], g2v[kSteps];
+#pragma unroll
+          for (int k = 0; k < kSteps; k++) {
+            const double nn = -3.0 + 0.25 * k;
+            const int x1 = (int)(x0 + (nn + 1) * nx);
+            const int y1 = (int)(y0 + (nn + 1) * ny);
+            const int x2 = (int)(x0 + (nn - 1) * nx);
+            const int y2 = (int)(y0 + (nn - 1) * ny);
+            const bool in = !(x1 < 0 || x1 >= g.W || y1 < 0 || y1 >= g.H) && !(x2 < 0 || x2 >= g.W || y2 < 0 || y2 >= g.H);
+            g1v[k] = -1;
+            g2v[k] = 0;
+            if (in) {
+              g1v[k] = (int)pix((size_t)y1 * g.W + x1);
+              g2v[k] = (int)pix((size_t)y2 * g.W + x2);
+            }
+          }
+          double Mn = 0, Mcount = 0;
+#pragma unroll
+          for (int k = 0; k < kSteps; k++) {
+            const double nn = -3.0 + 0.25 * k;
+            const int g1 = g1v[k], g2 = g2v[k];
+            if (g1 < g2) continue;  // also skips out-of-image steps (g1 = -1)
+            const double weight = (double)((g2 - g1) * (g2 - g1));
+            Mn += weight * nn;
+            Mcount += weight;
+          }
+          double bx = __longlong_as_double(0x7ff8deadbeef0000ll), by = 0;
+          if (Mcount != 0) {
+            const double n0 = Mn / Mcount;
+            bx = x0 + n0 * nx;
+            by = y0 + n0 * ny;
+            undistort(prm, &bx, &by);
+          }
+          if (t < kLdsRefine) {
+            S.sx[t] = bx;
+            S.sy[t] = by;
+          } else {
+            gsx[t - kLdsRefine] = bx;
+            gsy[t - kLdsRefine] = by;
+          }
+        }
+        team_sync<64>();
+        phase(1);
+        // per edge (lane e), the moments in the reference's sample order; samples are
+        // staged 8 at a time in registers so their LDS reads overlap
+        if (tid < 4) {
+          double Mx = 0, My = 0, Mxx = 0, Mxy = 0, Myy = 0, N = 0;
+          const int o = S.samp_off[tid];
+          const int ns = min(S.nsamp[tid], RCAP - o);
+          for (int c = 0; c < ns; c += 8) {
+            double xs[8], ys[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+              const int i = o + c + k;
+              xs[k] = __longlong_as_double(0x7ff8deadbeef0000ll);
+              ys[k] = 0;
+              if (c + k < ns) {
+                xs[k] = i < kLdsRefine ? S.sx[i] : gsx[i - kLdsRefine];
+                ys[k] = i < kLdsRefine ? S.sy[i] : gsy[i - kLdsRefine];
+              }
+            }
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+              const double bx = xs[k], by = ys[k];
+              if (isnan(bx)) continue;  // (also the padding past the edge's samples)
+              Mx += bx; My += by; Mxx += bx * bx; Mxy += bx * by; Myy += by * by; N++;
+            }
+          }
+          const double Ex = Mx / N, Ey = My / N;
+          const double Cxx = Mxx / N - Ex * Ex, Cxy = Mxy / N - Ex * Ey, Cyy = Myy / N - Ey * Ey;
+          const double nt = .5 * (double)det_atan2f_call((float)(-2 * Cxy), (float)(Cyy - Cxx));
+          S.lines[tid][0] = Ex;
+          S.lines[tid][1] = Ey;
+          S.lines[tid][2] = (double)det_cosf((float)nt);
+          S.lines[tid][3] = (double)det_sinf((float)nt);
+        }
+        team_sync<64>();
+        phase(2);
+        if (tid == 0) {
+          float qp[4][2];
+          for (int k = 0; k < 4; k++) { qp[k][0] = S.qc[k][0]; qp[k][1] = S.qc[k][1]; }
+          for (int i = 0; i < 4; i++) {
+            const int i1 = (i + 1) & 3;
+            const double A00 = S.lines[i][3], A01 = -S.lines[i1][3];
+            const double A10 = -S.lines[i][2], A11 = S.lines[i1][2];
+            const double B0 = -S.lines[i][0] + S.lines[i1][0];
+            const double B1 = -S.lines[i][1] + S.lines[i1][1];
+            const double det = A00 * A11 - A10 * A01;
+            if (fabs(det) > 0.001) {
+              const double W00 = A11 / det, W01 = -A01 / det;
+              const double L0 = W00 * B0 + W01 * B1;
+              double px = S.lines[i][0] + L0 * A00, py = S.lines[i][1] + L0 * A10;
+              redistort(prm, &px, &py);
+              qp[i1][0] = (float)px;
+              qp[i1][1] = (float)py;
+            }
+          }
+          for (int k = 0; k < 4; k++) { S.qc[k][0] = qp[k][0]; S.qc[k][1] = qp[k][1]; }
+        }
+        team_sync<64>();
+        phase(3);
+      }
+      if (AT_DIAG_STOP(prm, 6)) continue;
+      // ---- homography (quad_update_homographies / homography_compute2) -----------
+      if (homography_wave(S.qc, S.A, S.H) != 0) continue;
+      if (tid == 0) {
+        const double* H = S.H;
+        const double hdet = H[0] * (H[4] * H[8] - H[5] * H[7]) - H[1] * (H[3] * H[8] - H[5] * H[6]) +
+                            H[2] * (H[3] * H[7] - H[4] * H[6]);
+        S.ok = hdet != 0;
+      }
+      team_sync<64>();
+      phase(4);
+      if (!S.ok) continue;
+      uint32_t seq = 0;
+      if (POSE) {  // hand the homography and the unrotated corners to the pose wave
+        if (tid < 9) P.H[tid] = S.H[tid];
+        if (tid < 4) {
+          const int tcx = (tid == 1 || tid == 2) ? 1 : -1, tcy = tid < 2 ? 1 : -1;
+          hproject(S.H, tcx, tcy, &P.p[tid][0], &P.p[tid][1]);
+        }
+        seq = ++pose_seq;
+        team_sync<64>();
+        if (tid == 0) __hip_atomic_store(&P.seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      uint32_t bc = 0xffffffffu;
+      double margin_d = -1;
+      do {
+      // ---- quad_decode: border gray models (8 patterns x width_at_border <= 8
+      // samples: lane = 8 * pattern + sample) ----
+      const int wab = prm.fam.width_at_border, tw = prm.fam.total_width, nbits = prm.fam.nbits;
+      const int minc = (wab - tw) / 2;
+      {
+        const int pidx = tid >> 3, i = tid & 7;
+        float p0, p1, p2, p3;
+        border_pattern(pidx, (float)wab, p0, p1, p2, p3);
+        const double tagx01 = (double)((p0 + (float)i * p2) / (float)wab);
+        const double tagy01 = (double)((p1 + (float)i * p3) / (float)wab);
+        const double tagx = 2 * (tagx01 - 0.5), tagy = 2 * (tagy01 - 0.5);
+        double px, py;
+        hproject(S.H, tagx, tagy, &px, &py);
+        const int ix = (int)px, iy = (int)py;
+        S.gmx[tid] = tagx;
+        S.gmy[tid] = tagy;
+        S.gmvalid[tid] = i < wab && !(ix < 0 || iy < 0 || ix >= g.W || iy >= g.H);
+        S.gmv[tid] = S.gmvalid[tid] ? (double)pix((size_t)iy * g.W + ix) : 0.0;
+      }
+      for (int t = tid; t < tw * tw; t += kDecodeThreads) S.values[t] = 0;
+      team_sync<64>();
+      phase(5);
+      // lane 0 builds and solves the white model, lane 1 the black one, each over
+      // its 32 samples in the serial order, eight samples staged in registers at a time
+      double interp00 = 0;
+      if (tid < 2) {
+        GrayModel m;
+        for (int k = 0; k < 3; k++) {
+          m.B[k] = 0;
+          for (int j = 0; j < 3; j++) m.A[k][j] = 0;
+        }
+        for (int grp = 0; grp < 4; grp++) {
+          const int t0 = 16 * grp + 8 * tid;
+          double xs[8], ys[8], vs[8];
+          int ok[8];
+#pragma unroll
+          for (int i = 0; i < 8; i++) {
+            xs[i] = S.gmx[t0 + i];
+            ys[i] = S.gmy[t0 + i];
+            vs[i] = S.gmv[t0 + i];
+            ok[i] = S.gmvalid[t0 + i];
+          }
+#pragma unroll
+          for (int i = 0; i < 8; i++)
+            if (ok[i]) gm_add(m, xs[i], ys[i], vs[i]);
+        }
+        gm_solve(m);
+        double* C = tid == 0 ? S.wC : S.bC;
+        for (int k = 0; k < 3; k++) C[k] = m.C[k];
+        interp00 = gm_interp(m, 0, 0);
+      }
+      const double w00 = __shfl(interp00, 0), b00 = __shfl(interp00, 1);
+      team_sync<64>();
+      if (w00 - b00 < 0) break;  // uniform
+      phase(6);
+      if (tid < nbits) {
+        const int bity = prm.fam.bity[tid], bitx = prm.fam.bitx[tid];
+        const double tagx01 = (bitx + 0.5) / wab, tagy01 = (bity + 0.5) / wab;
+        const double tagx = 2 * (tagx01 - 0.5), tagy = 2 * (tagy01 - 0.5);
+        double px, py;
+        hproject(S.H, tagx, tagy, &px, &py);
+        const int x1 = (int)floor(px - 0.5), x2 = (int)ceil(px - 0.5);
+        const double xx = px - 0.5 - x1;
+        const int y1 = (int)floor(py - 0.5), y2 = (int)ceil(py - 0.5);
+        const double yy = py - 0.5 - y1;
+        if (!(x1 < 0 || x2 >= g.W || y1 < 0 || y2 >= g.H)) {  // value_for_pixel
+          const double v = (int)pix((size_t)y1 * g.W + x1) * (1 - xx) * (1 - yy) + (int)pix((size_t)y1 * g.W + x2) * xx * (1 - yy) +
+                           (int)pix((size_t)y2 * g.W + x1) * (1 - xx) * yy + (int)pix((size_t)y2 * g.W + x2) * xx * yy;
+          const double bth = S.bC[0] * tagx + S.bC[1] * tagy + S.bC[2];
+          const double wth = S.wC[0] * tagx + S.wC[1] * tagy + S.wC[2];
+          S.values[tw * (bity - minc) + bitx - minc] = v - (bth + wth) / 2.0;
+        }
+      }
+      team_sync<64>();
+      phase(7);
+      // sharpen (apriltag.c) over the total_width^2 grid: each lane owns cells t, t+64, t+128
+      constexpr int kShR = (kMaxTotalWidth * kMaxTotalWidth + kDecodeThreads - 1) / kDecodeThreads;
+      double shv[kShR];
+      // (the lane's cell indices recomputed per quad: hoisted out of the item loop they
+      // were spilled to scratch and reloaded here, one round trip each)
+      int tl = tid;
+      __asm__ volatile("" : "+v"(tl));
+#pragma unroll
+      for (int r = 0; r < kShR; r++) {
+        const int t = tl + 64 * r;
+        shv[r] = 0;
+        if (t < tw * tw) {
+          // the kernel {0,-1,0; -1,4,-1; 0,-1,0} in the reference's tap order, its zero taps
+          // left out: they add +-0, which changes no nonzero partial sum, and the sign of a
+          // zero sum reaches no decision (a value is never -0: v - m is +0 when v == m).
+          // The five reads are issued together (the 3x3 loop's reads went one at a time,
+          // their addresses spilled to scratch)
+          const int y = t / tw, x = t % tw;
+          const double up = S.values[y > 0 ? t - tw : t], left = S.values[x > 0 ? t - 1 : t], c = S.values[t];
+          const double right = S.values[x < tw - 1 ? t + 1 : t], down = S.values[y < tw - 1 ? t + tw : t];
+          double acc = 0;
+          if (y > 0) acc = acc - up;
+          if (x > 0) acc = acc - left;
+          acc = acc + c * 4;
+          if (x < tw - 1) acc = acc - right;
+          if (y < tw - 1) acc = acc - down;
+          shv[r] = acc;
+        }
+      }
+      team_sync<64>();
+#pragma unroll
+      for (int r = 0; r < kShR; r++) {
+        const int t = tid + 64 * r;
+        if (t < tw * tw) S.values[t] = S.values[t] + prm.decode_sharpening * shv[r];
+      }
+      team_sync<64>();
+      // code word and scores: lane i reads bit i's value, the scores run in bit
+      // order on every lane (uniform v_readlane loop), the word comes from a ballot
+      double bitv = 0;
+      if (tid < nbits) bitv = S.values[tw * (prm.fam.bity[tid] - minc) + prm.fam.bitx[tid] - minc];
+      const uint64_t white_bits = __ballot(tid < nbits && bitv > 0);  // bit i: data bit i (MSB first in the word)
+      const uint64_t rcode0 = __builtin_bitreverse64(white_bits) >> (64 - nbits);
+      {
+        float black_score = 0, white_score = 0, black_cnt = 1, white_cnt = 1;
+        for (int i = 0; i < nbits; i++) {
+          const double v = readlane_f64(bitv, i);
+          if (v > 0) { white_score = (float)(white_score + v); white_cnt++; }
+          else { black_score = (float)(black_score - v); black_cnt++; }
+        }
+        margin_d = fmin((double)(white_score / white_cnt), (double)(black_score / black_cnt));
+      }
+      phase(8);
+      // quick_decode_codeword: first rotation, then entry, within hamming <= 2
+      // (codes are >= 5 apart, so at most one entry matches a rotation)
+      {
+        uint64_t r[4];
+        r[0] = rcode0;
+#pragma unroll
+        for (int k = 1; k < 4; k++) r[k] = rotate90_n(r[k - 1], nbits);
+        // the codebook straight from HBM (L2-resident: every workgroup reads the same
+        // table; an LDS copy cost 8 KB per one-wave workgroup, and the LDS freed lets
+        // the concurrent batches' kernels co-reside: +2.8 % throughput, profiles/r03l),
+        // ten of a lane's entries loaded together (tag36h11: one round trip instead of 10)
+        constexpr int kBookChunk = 10;  // (every family in one round trip: ncodes <= 640)
+        for (int e0 = 0; e0 < prm.fam.ncodes; e0 += kBookChunk * kDecodeThreads) {
+          uint64_t cw[kBookChunk];
+#pragma unroll
+          for (int k = 0; k < kBookChunk; k++) {
+            const int ent = e0 + tid + kDecodeThreads * k;
+            cw[k] = ent < prm.fam.ncodes ? b.book_code[ent] : 0ull;
+          }
+#pragma unroll
+          for (int k = 0; k < kBookChunk; k++) {
+            const int ent = e0 + tid + kDecodeThreads * k;
+#pragma unroll
+            for (int rot = 0; rot < 4; rot++) {
+              const int hd = __popcll(r[rot] ^ cw[k]);
+              if (ent < prm.fam.ncodes && hd <= 2) bc = min(bc, (uint32_t)((rot << 24) | (hd << 16) | ent));
+            }
+          }
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) bc = min(bc, (uint32_t)__shfl_xor(bc, d));
+      }
+      } while (false);
+      if (POSE) {  // the pose of this quad is done before the next one is handed over
+        while (__hip_atomic_load(&P.ack, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seq)
+          __builtin_amdgcn_s_sleep(1);
+      }
+      if (tid == 0) {
+        const float margin = (float)margin_d;
+        if (margin >= 0 && bc != 0xffffffffu) {
+          const int rot = bc >> 24, hd = (bc >> 16) & 0xff, ent = bc & 0xffff;
+          DevDetection d;
+          d.id = b.book_id[ent];
+          d.hamming = hd;
+          d.decision_margin = margin;
+          d.blob_rank = (int32_t)qrank;
+          const double R[9] = {c_rot_c[rot], -c_rot_s[rot], 0, c_rot_s[rot], c_rot_c[rot], 0, 0, 0, 1};
+          for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+              double acc = 0;
+              for (int k = 0; k < 3; k++) acc += S.H[i * 3 + k] * R[k * 3 + j];
+              d.H[i * 3 + j] = acc;
+            }
+          hproject(d.H, 0, 0, &d.c[0], &d.c[1]);
+          for (int i = 0; i < 4; i++) {
+            const int tcx = (i == 1 || i == 2) ? 1 : -1;
+            const int tcy = (i < 2) ? 1 : -1;
+            hproject(d.H, tcx, tcy, &d.p[i][0], &d.p[i][1]);
+          }
+          d.frame = (uint16_t)f;
+          if (POSE) {
+            // R = R0 Rz(rot) with the exact quarter turn, t = t0
+            const int c = rot == 0 ? 1 : rot == 2 ? -1 : 0, sn = rot == 1 ? 1 : rot == 3 ? -1 : 0;
+            for (int i = 0; i < 3; i++) {
+              d.pose_R[i * 3 + 0] = P.R[i * 3 + 0] * c + P.R[i * 3 + 1] * sn;
+              d.pose_R[i * 3 + 1] = -P.R[i * 3 + 0] * sn + P.R[i * 3 + 1] * c;
+              d.pose_R[i * 3 + 2] = P.R[i * 3 + 2];
+            }
+            for (int k = 0; k < 3; k++) d.pose_t[k] = P.t[k];
+            d.pose_err[0] = P.err[0];
+            d.pose_err[1] = P.err[1];
+          }
+          // the frame's own slot; the first kDetPoolPerFrame also to the host mirror
+          // (POSE: complete; else the pose fields follow from k_pose)
+          const uint32_t k = atomicAdd(b.ndets + f, 1u);
+          if (k < (uint32_t)kMaxDets) {
+            const uint32_t slot = (uint32_t)f * kMaxDets + k;
+            b.dets[slot] = d;
+            if (k < (uint32_t)kDetPoolPerFrame) b.hdets[(uint32_t)f * kDetPoolPerFrame + k] = d;
+            if (!POSE) b.det_work[atomicAdd(b.det_head, 1u)] = slot;
+          } else {
+            atomicOr(b.status + f, kStatusDetsOverflow);  // (more candidates than quads: unreachable)
+          }
+        }
+      }
+      team_sync<64>();
+      phase(9);
+    }
+    probe_flush(b, prm, pacc, 128, tid == 0);
+    if (tid == 0) kt_end(b, 10);
+    if (POSE) {
+      if (tid == 0) __hip_atomic_store(&P.exit, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      decode_finish(b, tid, nq);
+    }
   }
 }
 
@@ -6692,7 +7318,15 @@ hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, i
     // for every quad of a full batch to start at once (16 per CU at 8.5 KB LDS)
     // (the experiment knob never exceeds the grid the refine scratch was sized for)
     const dim3 grd(prm.dec_wg ? std::min(prm.dec_wg, decode_grid(nblobwg, B)) : decode_grid(nblobwg, B));
+    // throughput mode: kDecRowLanes lanes per quad, four quads per wave, on the same
+    // grid; AT_DEC_LPQ=64 (experiment) keeps one per wave.  The mode is the detector's
+    // (g.ctw == 64, i.e. max_batch >= kWideBlobMaxBatch), not the launch's frame count: a
+    // throughput detector given 1-7 frames runs the packed kernel too, unless tag_size > 0
+    // and nothing is timed -- then the launch is pose-fused (above) and keeps the pose
+    // wave's one-quad kernel, as before.
+    const bool rows = g.ctw == 64 && !pose_fused && prm.dec_lpq != 64;
     if (on(10) && pose_fused) hipLaunchKernelGGL(k_decode<true>, grd, dim3(128), 0, st, b, g, prm, B, fmt);
+    else if (on(10) && rows) hipLaunchKernelGGL((k_decode<false, kDecRowLanes>), grd, dim3(kDecodeThreads), 0, st, b, g, prm, B, fmt);
     else if (on(10)) hipLaunchKernelGGL(k_decode<false>, grd, dim3(kDecodeThreads), 0, st, b, g, prm, B, fmt);
   }
   tk(10, st, 1);
