@@ -484,6 +484,68 @@ int at_jpeg_stats(at_detector *d, uint64_t *out, int cap);
 int at_jpeg_encode_host(const uint8_t *bgr, int width, int height, int quality, int sampling, uint8_t *out,
                         size_t cap, size_t *len);
 
+/* The preview stream: the annotated image small enough for a robot's radio link (the
+ * seasocks viewer's websocket, the bag recording's /compressed topic), for a frame of ANY
+ * input format -- YUYV and mono8 cameras and the luma-only MJPG route have no annotated
+ * image otherwise.
+ *
+ * Geometry (at_preview_size, host only): scale s is an integer 1..8; pw = (width / s) & ~7,
+ * ph = (height / s) & ~7 (the encoder's multiples of 8); the crop of pw * s x ph * s source
+ * pixels is centred, ox = (width - pw * s) / 2, oy likewise.  pw < 8 or ph < 8 (or s outside
+ * 1..8): AT_E_INVALID.  s = 1 is "convert only": the full-size annotated image.
+ *
+ * Image: every source pixel is converted to BGR8 (GRAY8: B = G = R = Y; YUYV: pixel x takes
+ * the U and V of its pair, 20-bit fixed-point BT.601 limited range:
+ *   y = max(0, Y - 16) * 1220542,  R = sat8((y + (1 << 19) + 1673527 (V - 128)) >> 20),
+ *   G = sat8((y + (1 << 19) - 852492 (V - 128) - 409993 (U - 128)) >> 20),
+ *   B = sat8((y + (1 << 19) + 2116026 (U - 128)) >> 20) -- OpenCV's COLOR_YUV2BGR_YUY2 as
+ * remembered; equality with cv::cvtColor is not pinned by a test), then averaged per channel
+ * over its s x s box, (sum + s * s / 2) / (s * s), integers only.  The records are mapped
+ * before anything is drawn -- corners and centre (p - o) / s in double, a box x' = (x - ox) / s,
+ * w' = w / s in float -- and drawn at pw x ph like the full-size image: boxes first, tag
+ * outlines on top, lines 2 px, id glyphs at their fixed size.
+ *
+ * at_preview_bgr / at_preview_jpeg take frame `frame` of the last batch where it was staged
+ * in HBM: AT_E_INVALID unless that batch was host-fed (at_detect*, at_enqueue_host,
+ * at_enqueue_mjpg with or without colour; a luma-only MJPG batch gives the decoded gray
+ * plane) and `frame` one of its frames.  A pending batch is waited for.  The staged frame is
+ * only read (unlike at_annotate_staged).  at_preview_jpeg_device takes one device-resident
+ * frame of the detector's geometry in `fmt` (at_enqueue_device batches): NULL or not 8-byte
+ * aligned is AT_E_INVALID.  The preview image lives in a buffer allocated on the first call.
+ *
+ * The JPEG is at_encode_jpeg_device's stream at pw x ph.  max_bytes == 0: one encode at
+ * `quality`.  max_bytes > 0, the per-frame byte budget: encode at `quality`; if that is
+ * larger, bisect on [1, quality - 1] (mid = (lo + hi + 1) / 2; lo = mid if it fits, else
+ * hi = mid - 1; until lo == hi) and return the encode at lo -- this rule, not "the best
+ * quality", is the contract, since JPEG size is not strictly monotonic in quality.  At most
+ * 2 + ceil(log2(quality - 1)) encodes: 8 from quality 50, 9 from 100.  If quality 1 does not
+ * fit: AT_E_CAPACITY, *len its size, *quality_used = 1, nothing written.  A stream larger than
+ * cap: AT_E_CAPACITY with *len the size needed, as at_annotate_jpeg.  *quality_used (may be
+ * NULL) is the quality of the stream returned.
+ *
+ * at_preview_host / at_preview_jpeg_host: the same on the CPU (no device; any w x h whose
+ * preview is at least 8 x 8, w even for YUYV; cap >= pw * ph * 3) through the same arithmetic,
+ * mapping and search -- the reference of the device path, bit for bit.
+ * at_preview_stats, the last preview call: [0] bytes returned, [1] quality used, [2] encodes
+ * run, [3] pw, [4] ph, [5] the kernels' time in nanoseconds (HIP events; while
+ * at_set_profiling is on, 0 otherwise).
+ * All calls are synchronous, on the detector's stream, outside the captured graphs. */
+int at_preview_size(int width, int height, int scale, int *pw, int *ph, int *ox, int *oy);
+int at_preview_bgr(at_detector *d, int frame, int scale, const at_detection *dets, int n, const at_gp_box *boxes,
+                   int nb, uint8_t *bgr_out);
+int at_preview_jpeg(at_detector *d, int frame, int scale, const at_detection *dets, int n, const at_gp_box *boxes,
+                    int nb, int quality, int sampling, size_t max_bytes, uint8_t *out, size_t cap, size_t *len,
+                    int *quality_used);
+int at_preview_jpeg_device(at_detector *d, const void *d_frame, at_pixfmt fmt, int scale, const at_detection *dets,
+                           int n, const at_gp_box *boxes, int nb, int quality, int sampling, size_t max_bytes,
+                           uint8_t *out, size_t cap, size_t *len, int *quality_used);
+int at_preview_host(const uint8_t *frame, at_pixfmt fmt, int w, int h, int scale, const at_detection *dets, int n,
+                    const at_gp_box *boxes, int nb, uint8_t *bgr_out, size_t cap);
+int at_preview_jpeg_host(const uint8_t *frame, at_pixfmt fmt, int w, int h, int scale, const at_detection *dets,
+                         int n, const at_gp_box *boxes, int nb, int quality, int sampling, size_t max_bytes,
+                         uint8_t *out, size_t cap, size_t *len, int *quality_used);
+int at_preview_stats(at_detector *d, uint64_t *out, int cap);
+
 /* Page-locked host memory (hipHostMalloc) for buffers the detector copies into on
  * its stream by DMA, e.g. at_annotate_staged's bgr_out: a pageable destination
  * goes through the runtime's staging buffers instead.  (No counterpart in the

@@ -10,12 +10,16 @@
 // outlined bgr8 image of the last frame (bgr8 input, or MJPG with --mjpg-color: the
 // frame's colour is then decoded on the GPU too).  --jpeg-out DIR: the outlined image is
 // JPEG-encoded on the GPU (DetectorCore::set_image_jpeg, --jpeg-quality Q, default 95) and
-// every frame's file written to DIR/frame_NNNNNN.jpg.
+// every frame's file written to DIR/frame_NNNNNN.jpg.  --preview-out DIR --preview-scale N: every
+// frame of ANY format also gives the scaled annotated JPEG (DetectorCore::set_preview,
+// --preview-quality Q, default 50, --preview-max-bytes B, default 0: no budget), written to
+// DIR/preview_NNNNNN.jpg (no file for a frame that fits the budget at no quality).
 //
 // usage: at_mock_node --camera-serial S --format bgr8|yuyv|gray|mjpg --frames F [--count N]
 //        [--vision-config-dir D] [--pin-to-core C --priority P]
 //        [--measurement-csv PATH] [--proto-out P] [--image-out I] [--device K] [--time N]
 //        [--mjpg-color] [--mjpg-device-entropy] [--jpeg-out DIR] [--jpeg-quality Q]
+//        [--preview-out DIR --preview-scale N [--preview-quality Q] [--preview-max-bytes B]]
 //   As the reference node (apriltags_cuda_detector.cu:137-193): the frame size, the
 //   intrinsics and the extrinsics come from the camera serial's records in the
 //   vision_config_data share directory, found through $AMENT_PREFIX_PATH
@@ -88,7 +92,9 @@ std::vector<Span> split_mjpg(const std::vector<uint8_t>& d) {
 int main(int argc, char** argv) {
   int W = 0, H = 0, count = -1, device = 0, pin = -1, priority = 80, time_n = 0, jpeg_quality = 95;
   std::string fmt_s = "yuyv", frames_path, calib_dir, serial = "N/A", sys_cfg, csv, proto_out, image_out, share_dir;
-  std::string jpeg_out;
+  std::string jpeg_out, preview_out;
+  int preview_scale = 0, preview_quality = 50;
+  long long preview_max_bytes = 0;
   bool mjpg_color = false, mjpg_device_entropy = false;
   for (int i = 1; i < argc; i += 2) {
     const std::string k = argv[i];
@@ -117,6 +123,10 @@ int main(int argc, char** argv) {
     else if (k == "--time") time_n = std::atoi(v.c_str());
     else if (k == "--jpeg-out") jpeg_out = v;
     else if (k == "--jpeg-quality") jpeg_quality = std::atoi(v.c_str());
+    else if (k == "--preview-out") preview_out = v;
+    else if (k == "--preview-scale") preview_scale = std::atoi(v.c_str());
+    else if (k == "--preview-quality") preview_quality = std::atoi(v.c_str());
+    else if (k == "--preview-max-bytes") preview_max_bytes = std::atoll(v.c_str());
     else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
   }
   at_node::Params prm;
@@ -188,6 +198,14 @@ int main(int argc, char** argv) {
     if (!jpeg_out.empty()) {
       core.set_image_jpeg(jpeg_quality);
       ::mkdir(jpeg_out.c_str(), 0777);  // (exists already: fine)
+    }
+    if (!preview_out.empty()) {
+      if (preview_scale < 1 || preview_max_bytes < 0) {
+        std::fprintf(stderr, "--preview-out needs --preview-scale 1..8 (and --preview-max-bytes >= 0)\n");
+        return 2;
+      }
+      core.set_preview(preview_scale, preview_quality, (size_t)preview_max_bytes);
+      ::mkdir(preview_out.c_str(), 0777);  // (exists already: fine)
     }
     at_node::FrameOutputs out;
     at_node::ImageBuffer image;
@@ -267,6 +285,16 @@ int main(int argc, char** argv) {
         jo.write((const char*)image.data(), (std::streamsize)image.size());
         if (!jo) {
           std::fprintf(stderr, "cannot write %s%s\n", jpeg_out.c_str(), name);
+          return 1;
+        }
+      }
+      if (!preview_out.empty() && !out.preview_jpeg.empty()) {
+        char name[32];
+        std::snprintf(name, sizeof(name), "/preview_%06d.jpg", f);
+        std::ofstream jo(preview_out + name, std::ios::binary);
+        jo.write((const char*)out.preview_jpeg.data(), (std::streamsize)out.preview_jpeg.size());
+        if (!jo) {
+          std::fprintf(stderr, "cannot write %s%s\n", preview_out.c_str(), name);
           return 1;
         }
       }

@@ -547,6 +547,41 @@ void DetectorCore::set_image_jpeg(int quality) {
   image_jpeg_ = quality;
 }
 
+// the preview's options checked and its page-locked buffer sized (shared by the two cores)
+static void preview_setup(int width, int height, int scale, int quality, ImageBuffer* buf) {
+  if (scale < 0 || scale > 8) throw std::runtime_error("set_preview: scale 1..8 (0: off)");
+  if (!scale) return;
+  if (quality < 1 || quality > 100) throw std::runtime_error("set_preview: quality 1..100");
+  int pw = 0, ph = 0;
+  const size_t most = at_preview_size(width, height, scale, &pw, &ph, nullptr, nullptr) == AT_OK
+                          ? at_jpeg_max_bytes(pw, ph, AT_JPEG_420)
+                          : 0;
+  if (!most) throw std::runtime_error("set_preview: no preview of this frame size at this scale");
+  buf->resize(most);
+}
+
+// the preview of the frame the last at_detect* staged; a frame that fits the budget at no quality
+// has none (AT_OK, *out empty)
+static int preview_encode(at_detector* det, int scale, int quality, size_t max_bytes, const at_detection* dets, int n,
+                          const at_gp_box* boxes, int nb, ImageBuffer* buf, std::vector<uint8_t>* out) {
+  out->clear();
+  size_t len = 0;
+  int used = 0;
+  const int rc = at_preview_jpeg(det, 0, scale, dets, n, boxes, nb, quality, AT_JPEG_420, max_bytes, buf->data(),
+                                 buf->size(), &len, &used);
+  if (rc == AT_E_CAPACITY && max_bytes) return AT_OK;
+  if (rc != AT_OK) return rc;
+  out->assign(buf->begin(), buf->begin() + (ptrdiff_t)len);
+  return AT_OK;
+}
+
+void DetectorCore::set_preview(int scale, int quality, size_t max_bytes) {
+  preview_setup(width_, height_, scale, quality, &preview_buf_);
+  preview_scale_ = scale;
+  preview_quality_ = quality;
+  preview_max_bytes_ = max_bytes;
+}
+
 // fmt < 0: `frame` is one MJPG frame of `len` bytes (at_detect_mjpg); the tail is the same
 int DetectorCore::run(const uint8_t* frame, size_t len, int fmt, double stamp_s, double receive_s, FrameOutputs* out,
                       ImageBuffer* annotate) {
@@ -577,6 +612,12 @@ int DetectorCore::run(const uint8_t* frame, size_t len, int fmt, double stamp_s,
     out->robot.push_back({d.id, d.robot[0], d.robot[1], d.robot[2]});
   }
   out->proto = encode_apriltag_list(out->tags.data(), (int)out->tags.size(), stamp_s);
+  if (preview_scale_) {
+    // every format; first, since the annotation below is drawn on the staged frame itself
+    const int prc = preview_encode(det_, preview_scale_, preview_quality_, preview_max_bytes_, out->detections.data(),
+                                   n, nullptr, 0, &preview_buf_, &out->preview_jpeg);
+    if (prc != AT_OK) return prc;
+  }
   if (annotate && (fmt == AT_FMT_BGR8 || fmt < 0)) {
     // draw_detection_outlines (:411) on the GPU, on the copy of the frame at_detect
     // staged in HBM: no host copy of the frame, no host drawing (an MJPG frame with
@@ -610,6 +651,15 @@ int DetectorCore::run(const uint8_t* frame, size_t len, int fmt, double stamp_s,
     }
     // image_pub_queue_->enqueue (:514-518): the queue owns a copy
     image_queue_->enqueue(StampedImage{std::vector<uint8_t>(annotate->begin(), annotate->end()), stamp_s});
+  }
+  if (publish_preview && !out->preview_jpeg.empty()) {
+    if (!preview_queue_) {
+      auto pub = publish_preview;
+      void* c = ctx;
+      preview_queue_.reset(new PublisherQueue<StampedImage>(
+          [pub, c](const StampedImage& img) { pub(c, img.bgr, img.stamp_s); }, 2));
+    }
+    preview_queue_->enqueue(StampedImage{out->preview_jpeg, stamp_s});
   }
   const auto pi1 = clk::now();
   if (csv_) {  // latency,det,publish_pose,publish_camera_pose,publish_image,networktables,processing (:526-552)
@@ -656,6 +706,13 @@ void GamePieceCore::set_image_jpeg(int quality) {
   image_jpeg_ = quality;
 }
 
+void GamePieceCore::set_preview(int scale, int quality, size_t max_bytes) {
+  preview_setup(width_, height_, scale, quality, &preview_buf_);
+  preview_scale_ = scale;
+  preview_quality_ = quality;
+  preview_max_bytes_ = max_bytes;
+}
+
 int GamePieceCore::process(const uint8_t* bgr, double stamp_s, GamePieceOutputs* out, ImageBuffer* annotate) {
   *out = GamePieceOutputs{};
   int ntags = 0;
@@ -680,6 +737,12 @@ int GamePieceCore::process(const uint8_t* bgr, double stamp_s, GamePieceOutputs*
     out->class_names.push_back(b.cls >= 0 && (size_t)b.cls < params_.class_names.size() ? params_.class_names[b.cls]
                                                                                          : "unknown");
   if (publish_detections) publish_detections(ctx, *out, stamp_s);
+  if (preview_scale_) {  // (before the boxes are drawn on the staged frame itself)
+    rc = preview_encode(det_, preview_scale_, preview_quality_, preview_max_bytes_, nullptr, 0, out->boxes.data(), n,
+                        &preview_buf_, &out->preview_jpeg);
+    if (rc != AT_OK) return rc;
+    if (publish_preview && !out->preview_jpeg.empty()) publish_preview(ctx, out->preview_jpeg, stamp_s);
+  }
   if (annotate) {
     if (image_jpeg_) {
       size_t len = 0;

@@ -92,6 +92,7 @@ struct FrameOutputs {
   std::string proto;                              // serialized ApriltagListProto
   int status = AT_OK;                             // at_detect return code
   int64_t det_time_us = 0;
+  std::vector<uint8_t> preview_jpeg;              // set_preview: the scaled annotated JPEG (empty: none)
 };
 
 // calibrationmatrix_<serial>.json: "matrix" 3x3 and "disto" [[k1 k2 p1 p2 k3]].
@@ -261,6 +262,16 @@ class DetectorCore {
   void set_image_jpeg(int quality);
   int image_jpeg() const { return image_jpeg_; }
   std::string compressed_image_topic() const { return params_.publish_images_to_topic + "/compressed"; }
+  // set_preview(scale, quality, max_bytes), scale 1..8 (0: off, the default): every frame, whatever
+  // its format -- yuyv, mono8 and MJPG without colour included, which have no annotated image
+  // otherwise -- is also scaled down by `scale` on the GPU, annotated at that scale and JPEG-encoded
+  // at `quality` (at_preview_jpeg, 4:2:0; with max_bytes > 0 the quality is lowered until the stream
+  // fits, and a frame nothing fits has no preview).  FrameOutputs::preview_jpeg receives the file and
+  // publish_preview gets it from a drop-oldest publisher queue of its own: a CompressedImage on
+  // preview_topic().  The frame staged in HBM is only read, before any annotation is drawn on it.
+  void set_preview(int scale, int quality = 50, size_t max_bytes = 0);
+  int preview_scale() const { return preview_scale_; }
+  std::string preview_topic() const { return params_.publish_images_to_topic + "/preview/compressed"; }
 
   const Params& params() const { return params_; }
   int width() const { return width_; }
@@ -268,7 +279,10 @@ class DetectorCore {
   // images the publisher queue dropped (a subscriber slower than the frame rate)
   size_t images_dropped() const { return image_queue_ ? image_queue_->dropped() : 0; }
   // waits until the publisher queue has handed every queued image to publish_image
-  void flush_images() { image_queue_.reset(); }
+  void flush_images() {
+    image_queue_.reset();
+    preview_queue_.reset();
+  }
   std::string pose_topic() const { return params_.publish_pose_to_topic; }
   std::string camera_pose_topic() const { return params_.publish_pose_to_topic + "_camera"; }
   const std::string& csv_path() const { return csv_path_; }
@@ -278,6 +292,8 @@ class DetectorCore {
   void (*publish_camera)(void* ctx, const std::vector<TagDetectionMsg>&) = nullptr;
   // called on the publisher-queue thread with the annotated image and its frame's stamp
   void (*publish_image)(void* ctx, const std::vector<uint8_t>&, double stamp_s) = nullptr;
+  // ... with the preview's JPEG file (set_preview)
+  void (*publish_preview)(void* ctx, const std::vector<uint8_t>&, double stamp_s) = nullptr;
   void (*send_networktables)(void* ctx, const std::vector<double>&, const std::string& proto) = nullptr;
   void* ctx = nullptr;
 
@@ -295,6 +311,10 @@ class DetectorCore {
     double stamp_s = 0;
   };
   std::unique_ptr<PublisherQueue<StampedImage>> image_queue_;
+  int preview_scale_ = 0, preview_quality_ = 50;
+  size_t preview_max_bytes_ = 0;
+  ImageBuffer preview_buf_;  // page-locked, at_jpeg_max_bytes of the preview: allocated by set_preview
+  std::unique_ptr<PublisherQueue<StampedImage>> preview_queue_;
   double R_[9], t_[3];
   at_detector* det_ = nullptr;
   std::vector<at_detection> dets_;
@@ -329,6 +349,7 @@ struct GamePieceOutputs {
   std::vector<at_gp_box> boxes;          // camera pixels, NMS order
   std::vector<std::string> class_names;  // of each box
   int status = AT_OK;                    // AT_E_CAPACITY: more than AT_GP_MAX_CANDIDATES candidates, no boxes
+  std::vector<uint8_t> preview_jpeg;     // set_preview: the scaled frame with the boxes, as JPEG (empty: none)
 };
 
 // imageCallback (:274-297) with everything between the frame's upload and the boxes' download
@@ -350,10 +371,16 @@ class GamePieceCore {
   void set_image_jpeg(int quality);  // 1..100; 0: off (the default)
   int image_jpeg() const { return image_jpeg_; }
   std::string compressed_image_topic() const { return params_.publish_to_topic + "/compressed"; }
+  // as DetectorCore::set_preview, with the boxes on the preview; publish_preview is called with
+  // it before process returns
+  void set_preview(int scale, int quality = 50, size_t max_bytes = 0);
+  int preview_scale() const { return preview_scale_; }
+  std::string preview_topic() const { return params_.publish_to_topic + "/preview/compressed"; }
   const GamePieceParams& params() const { return params_; }
 
   void (*publish_detections)(void* ctx, const GamePieceOutputs&, double stamp_s) = nullptr;
   void (*publish_image)(void* ctx, const std::vector<uint8_t>&, double stamp_s) = nullptr;
+  void (*publish_preview)(void* ctx, const std::vector<uint8_t>&, double stamp_s) = nullptr;
   void* ctx = nullptr;
 
  private:
@@ -363,6 +390,9 @@ class GamePieceCore {
   void* infer_ctx_;
   int image_jpeg_ = 0;
   ImageBuffer jpeg_buf_;
+  int preview_scale_ = 0, preview_quality_ = 50;
+  size_t preview_max_bytes_ = 0;
+  ImageBuffer preview_buf_;
   at_detector* det_ = nullptr;
   std::vector<at_detection> tags_;  // (the staging call's tag detections: not used here)
   std::vector<at_gp_box> boxes_;

@@ -10,7 +10,10 @@
 // queue -- or, with the parameter image_jpeg set to a quality 1..100 (default 0: off), the
 // same image JPEG-encoded on the GPU as a sensor_msgs/CompressedImage on
 // <publish_images_to_topic>/compressed (the topic the bag recording and the viewer read)
-// and nothing on the raw topic.  Set-up as the reference's (apriltags_cuda_detector.cu:137-193, 601-605): frame
+// and nothing on the raw topic.  With preview_scale 1..8 (default 0: off) every frame, whatever
+// its encoding, also gives the scaled annotated JPEG (preview_quality, default 50, lowered until
+// it fits preview_max_bytes when that is above 0) as a CompressedImage on
+// <publish_images_to_topic>/preview/compressed.  Set-up as the reference's (apriltags_cuda_detector.cu:137-193, 601-605): frame
 // W x H, intrinsics and extrinsics from the camera serial's records in
 // vision_config_data's share directory (ament_index), then CPU pinning + SCHED_FIFO.
 // The launch file (launch_vision.py:283-305) passes nothing else.
@@ -43,6 +46,9 @@ class ApriltagsAmdNode : public rclcpp::Node {
     p.timing_csv_path = declare_parameter<std::string>("timing_csv_path", p.timing_csv_path);
     const int image_jpeg = declare_parameter<int>("image_jpeg", 0);
     const bool mjpg_device_entropy = declare_parameter<bool>("mjpg_device_entropy", false);
+    const int preview_scale = declare_parameter<int>("preview_scale", 0);
+    const int preview_quality = declare_parameter<int>("preview_quality", 50);
+    const int preview_max_bytes = declare_parameter<int>("preview_max_bytes", 0);
     // optional override of the share directory (not passed by the launch file)
     std::string share_dir = declare_parameter<std::string>("vision_config_dir", "");
     if (share_dir.empty()) {
@@ -94,6 +100,18 @@ class ApriltagsAmdNode : public rclcpp::Node {
       msg->data = bgr;
       self->image_pub_->publish(std::move(msg));
     };
+    if (preview_scale) {
+      core_->set_preview(preview_scale, preview_quality, preview_max_bytes > 0 ? (size_t)preview_max_bytes : 0);
+      core_->publish_preview = [](void* c, const std::vector<uint8_t>& jpg, double stamp_s) {
+        auto* self = static_cast<ApriltagsAmdNode*>(c);  // publisher-queue thread
+        auto jmsg = std::make_unique<sensor_msgs::msg::CompressedImage>();
+        jmsg->header.stamp = rclcpp::Time(static_cast<int64_t>(stamp_s * 1e9));
+        jmsg->header.frame_id = "apriltag_detections";
+        jmsg->format = "jpeg";
+        jmsg->data = jpg;
+        self->preview_pub_->publish(std::move(jmsg));
+      };
+    }
     width_ = width;
     height_ = height;
     auto qos = rclcpp::QoS(1).best_effort().durability_volatile().deadline(std::chrono::milliseconds(50));
@@ -105,6 +123,8 @@ class ApriltagsAmdNode : public rclcpp::Node {
       compressed_pub_ = create_publisher<sensor_msgs::msg::CompressedImage>(core_->compressed_image_topic(), 10);
     else
       image_pub_ = create_publisher<sensor_msgs::msg::Image>(p.publish_images_to_topic, 10);
+    if (preview_scale)
+      preview_pub_ = create_publisher<sensor_msgs::msg::CompressedImage>(core_->preview_topic(), 10);
     std::string sched_log;  // applyCpuPinningAndScheduling (:601-605)
     at_node::apply_cpu_pinning_and_scheduling(p.pin_to_core, p.priority, &sched_log);
     RCLCPP_INFO(get_logger(), "%s", sched_log.c_str());
@@ -164,7 +184,7 @@ class ApriltagsAmdNode : public rclcpp::Node {
   at_node::ImageBuffer image_;  // page-locked: the annotated image arrives by DMA
   rclcpp::Publisher<apriltags_cuda::msg::TagDetectionArray>::SharedPtr pose_pub_, camera_pose_pub_;
   rclcpp::Publisher<sensor_msgs::msg::Image>::SharedPtr image_pub_;
-  rclcpp::Publisher<sensor_msgs::msg::CompressedImage>::SharedPtr compressed_pub_;
+  rclcpp::Publisher<sensor_msgs::msg::CompressedImage>::SharedPtr compressed_pub_, preview_pub_;
   // after the publishers: destroyed first (members go in reverse order), so the
   // publisher-queue thread never outlives image_pub_
   std::unique_ptr<at_node::DetectorCore> core_;

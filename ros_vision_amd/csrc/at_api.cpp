@@ -24,6 +24,7 @@
 #include "at_gp.h"
 #include "at_mjpg.h"
 #include "at_mjpg_entropy.h"
+#include "at_preview.h"
 
 namespace at {
 hipError_t launch_tap_sizes(const uint8_t* thr, const uint32_t* par, const uint32_t* size, uint32_t* out, int Wd,
@@ -31,6 +32,7 @@ hipError_t launch_tap_sizes(const uint8_t* thr, const uint32_t* par, const uint3
 hipError_t launch_tap_labels(const uint8_t* thr, const uint32_t* par, uint32_t* out, int Wd, int Hd, hipStream_t st);
 hipError_t launch_gp_preprocess(const uint8_t* src, int w, int h, float* out, int ow, int oh, int c, hipStream_t st);
 hipError_t launch_draw(const DrawPrim* prims, int n, uint32_t* last, uint8_t* bgr, int W, int H, hipStream_t st);
+hipError_t launch_preview(const uint8_t* src, int fmt, int W, int H, int s, uint8_t* dst, hipStream_t st);
 hipError_t launch_mjpg_idct(const uint8_t* coef, size_t slot, uint8_t* out, size_t out_stride, int W, int H,
                             int nframes, hipStream_t st);
 hipError_t launch_mjpg_color(const uint8_t* coef, size_t slot, const uint8_t* gray, uint8_t* planes,
@@ -242,9 +244,9 @@ struct at_detector {
   at::JpgBufs jpg;
   size_t jpg_out_cap;       // bytes of jpg.out
   uint32_t* h_jpg_total;    // mapped, page-locked: where k_jpg_pack leaves the length
-  uint8_t jpg_hdr[at::kJpgHeaderMax];  // SOI .. SOS of the last (quality, sampling)
+  uint8_t jpg_hdr[at::kJpgHeaderMax];  // SOI .. SOS of the last (quality, sampling, width, height)
   size_t jpg_hdr_len;
-  int jpg_hdr_q, jpg_hdr_s;
+  int jpg_hdr_q, jpg_hdr_s, jpg_hdr_w, jpg_hdr_h;
   uint64_t jpg_stats[2];    // last encode: bytes out, the encode kernels' ns (while profiling)
   hipEvent_t ev_jpg[2];     // around them (created on first use)
   // game-piece output parse (at_gp_parse_device), allocated on the first call for max_batch
@@ -254,6 +256,11 @@ struct at_detector {
   uint32_t* h_gp_info;      // [B][2] ... and of gp.info: boxes kept, candidates
   uint64_t gp_stats[4];     // last call: candidates, most of one frame, boxes kept, kernel ns (while profiling)
   hipEvent_t ev_gp[2];      // around the two kernels (created on first use)
+  // preview (at_preview_bgr / at_preview_jpeg): the pw x ph BGR8 image, allocated on the first
+  // call at width * height * 3 (s = 1) and kept
+  uint8_t* d_pv;
+  uint64_t pv_stats[6];     // last call: bytes, quality used, encodes, pw, ph, kernels' ns (while profiling)
+  hipEvent_t ev_pv[2];      // around k_preview and the drawing (created on first use)
 };
 
 // Experiment and diagnostic knobs (stage cut-offs, grid / tile overrides, phase
@@ -368,6 +375,9 @@ void at_destroy(at_detector* d) {
   if (d->h_jpg_total) (void)hipHostFree(d->h_jpg_total);
   for (hipEvent_t e : d->ev_gp)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : d->ev_pv)
+    if (e) (void)hipEventDestroy(e);
+  if (d->d_pv) (void)hipFree(d->d_pv);
   if (d->h_gp_out) (void)hipHostFree(d->h_gp_out);
   if (d->h_gp_info) (void)hipHostFree(d->h_gp_info);
   if (d->ev_done) (void)hipEventDestroy(d->ev_done);
@@ -1474,61 +1484,18 @@ int at_tag_detections(const at_pose* poses, int n, const double* extr_R, const d
 }
 
 // ---- annotated image ------------------------------------
-// The segments of node/at_node.cpp's draw_detection_outlines, in its drawing order:
-// per detection the four sides (apriltag_utils.cu:58-65: corners truncated to int
-// as cv::Point does; 0-1 green, 0-3 red, 1-2 and 2-3 blue), then the id's digit
-// strokes centred on c (:67-77).  The digit strokes are the node's.
-static void outline_prims(const at_detection* dets, int n, std::vector<DrawPrim>* out) {
-  static const uint8_t kGreen[3] = {0, 0xff, 0}, kRed[3] = {0, 0, 0xff}, kBlue[3] = {0xff, 0, 0},
-                       kText[3] = {0xff, 0x99, 0};
-  static const std::vector<std::vector<std::pair<int, int>>> kDigits[10] = {
-      {{{0, 1}, {1, 0}, {3, 0}, {4, 1}, {4, 7}, {3, 8}, {1, 8}, {0, 7}, {0, 1}}},
-      {{{1, 2}, {2, 0}, {2, 8}}, {{1, 8}, {3, 8}}},
-      {{{0, 1}, {1, 0}, {3, 0}, {4, 1}, {4, 3}, {0, 8}, {4, 8}}},
-      {{{0, 0}, {4, 0}, {2, 3}, {3, 3}, {4, 4}, {4, 7}, {3, 8}, {1, 8}, {0, 7}}},
-      {{{3, 8}, {3, 0}, {0, 5}, {4, 5}}},
-      {{{4, 0}, {0, 0}, {0, 3}, {3, 3}, {4, 4}, {4, 7}, {3, 8}, {0, 8}}},
-      {{{4, 0}, {2, 0}, {0, 3}, {0, 7}, {1, 8}, {3, 8}, {4, 7}, {4, 5}, {3, 4}, {0, 4}}},
-      {{{0, 0}, {4, 0}, {1, 8}}},
-      {{{1, 4}, {0, 3}, {0, 1}, {1, 0}, {3, 0}, {4, 1}, {4, 3}, {3, 4}, {1, 4}, {0, 5}, {0, 7}, {1, 8},
-        {3, 8}, {4, 7}, {4, 5}, {3, 4}}},
-      {{{4, 4}, {1, 4}, {0, 3}, {0, 1}, {1, 0}, {3, 0}, {4, 1}, {4, 5}, {2, 8}, {0, 8}}},
-  };
-  auto seg = [&](double x0, double y0, double x1, double y1, const uint8_t c[3]) {
-    DrawPrim q;
-    q.x0 = x0; q.y0 = y0; q.x1 = x1; q.y1 = y1;
-    q.bgr[0] = c[0]; q.bgr[1] = c[1]; q.bgr[2] = c[2];
-    out->push_back(q);
-  };
-  for (int i = 0; i < n; i++) {
-    const at_detection& d = dets[i];
-    auto P = [&](int k, int c) { return (double)(int)d.p[k][c]; };
-    seg(P(0, 0), P(0, 1), P(1, 0), P(1, 1), kGreen);
-    seg(P(0, 0), P(0, 1), P(3, 0), P(3, 1), kRed);
-    seg(P(1, 0), P(1, 1), P(2, 0), P(2, 1), kBlue);
-    seg(P(2, 0), P(2, 1), P(3, 0), P(3, 1), kBlue);
-    const std::string text = std::to_string(d.id);
-    const double sc = 2.5, adv = 7 * sc;
-    const double tw = adv * text.size() - 2 * sc, th = 8 * sc;
-    const double ox = (int)(d.c[0] - tw / 2), oy = (int)(d.c[1] - th / 2);
-    for (size_t k = 0; k < text.size(); ++k) {
-      if (text[k] < '0' || text[k] > '9') continue;
-      for (const auto& stroke : kDigits[text[k] - '0'])
-        for (size_t t = 1; t < stroke.size(); ++t)
-          seg(ox + k * adv + stroke[t - 1].first * sc, oy + stroke[t - 1].second * sc, ox + k * adv + stroke[t].first * sc,
-              oy + stroke[t].second * sc, kText);
-    }
-  }
-}
+// (outline_prims, the segments of node/at_node.cpp's draw_detection_outlines: at_preview.cpp)
 
 // segments drawn onto `bgr` on the detector's stream (not waited for)
-static int draw_prims(at_detector* d, const std::vector<DrawPrim>& prims, uint8_t* bgr) {
+// (dw x dh: the image's size, the detector's geometry or a preview's inside it; 0: the detector's)
+static int draw_prims(at_detector* d, const std::vector<DrawPrim>& prims, uint8_t* bgr, int dw = 0, int dh = 0) {
   HIPCHK(hipSetDevice(d->device));
   if (prims.empty()) return AT_OK;
-  const size_t W = (size_t)d->g.W, H = (size_t)d->g.H;
+  const size_t W = dw ? (size_t)dw : (size_t)d->g.W, H = dh ? (size_t)dh : (size_t)d->g.H;
   if (!d->d_last) {
-    HIPCHK(hipMalloc((void**)&d->d_last, W * H * 4));
-    HIPCHK(hipMemset(d->d_last, 0, W * H * 4));  // kept zero by the paint pass
+    const size_t full = (size_t)d->g.W * d->g.H;
+    HIPCHK(hipMalloc((void**)&d->d_last, full * 4));
+    HIPCHK(hipMemset(d->d_last, 0, full * 4));  // kept zero by the paint pass
   }
   if (prims.size() > d->prims_cap) {
     if (d->d_prims) HIPCHK(hipFree(d->d_prims));
@@ -1686,33 +1653,12 @@ int at_gp_parse_stats(at_detector* d, uint64_t* out, int cap) {
   return n;
 }
 
-// The rectangle of detection_test.cpp:84-100 as four 2-px segments in the class colour
-// (top, right, bottom, left), as node/at_node.cpp's draw_boxes draws them.
-// (node/at_node.cpp's draw_boxes restates gp_trunc, the clamp and the palette of at_gp.h on its
-// own: change one, change the other -- tests/test_gp_parse_gpu.py compares the pixels.)
-static void box_prims(const at_detector* d, const at_gp_box* boxes, int n, std::vector<DrawPrim>* out) {
-  std::vector<DrawPrim>& prims = *out;
-  prims.reserve((size_t)n * 4);
-  for (int i = 0; i < n; i++) {
-    GpBox b;
-    memcpy(&b, boxes + i, sizeof(b));
-    int x1, y1, x2, y2;
-    gp_box_corners(b, d->g.W, d->g.H, &x1, &y1, &x2, &y2);
-    const uint8_t* c = kGpPalette[((b.cls % 6) + 6) % 6];
-    const int seg[4][4] = {{x1, y1, x2, y1}, {x2, y1, x2, y2}, {x2, y2, x1, y2}, {x1, y2, x1, y1}};
-    for (const auto& s : seg) {
-      DrawPrim q;
-      q.x0 = s[0]; q.y0 = s[1]; q.x1 = s[2]; q.y1 = s[3];
-      q.bgr[0] = c[0]; q.bgr[1] = c[1]; q.bgr[2] = c[2];
-      prims.push_back(q);
-    }
-  }
-}
+// (box_prims, the rectangle as four 2-px segments in the class colour: at_preview.cpp)
 
 int at_gp_draw_boxes_device(at_detector* d, const at_gp_box* boxes, int n, uint8_t* bgr) {
   if (!d || n < 0 || (n > 0 && !boxes) || !bgr) return AT_E_INVALID;
   std::vector<DrawPrim> prims;
-  box_prims(d, boxes, n, &prims);
+  box_prims(d->g.W, d->g.H, boxes, n, &prims);
   const int rc = draw_prims(d, prims, bgr);
   if (rc != AT_OK) return rc;
   HIPCHK(hipStreamSynchronize(d->st));
@@ -1735,7 +1681,7 @@ int at_gp_annotate_staged(at_detector* d, int frame, const at_gp_box* boxes, int
   int rc = gp_staged_image(d, frame, &img);
   if (rc != AT_OK) return rc;
   std::vector<DrawPrim> prims;
-  box_prims(d, boxes, n, &prims);
+  box_prims(d->g.W, d->g.H, boxes, n, &prims);
   rc = draw_prims(d, prims, img);
   if (rc != AT_OK) return rc;
   HIPCHK(hipMemcpyAsync(bgr_out, img, (size_t)d->g.W * d->g.H * 3, hipMemcpyDeviceToHost, d->st));
@@ -1798,17 +1744,23 @@ static int jpeg_prepare(at_detector* d) {
 
 // `img` (device, the detector's geometry) encoded on the detector's stream behind what is
 // queued there; returns when the bytes are in `out`
+// (ew x eh: the image's size, the detector's geometry or a preview's inside it; 0: the detector's)
 static int encode_jpeg(at_detector* d, const uint8_t* img, int quality, int sampling, uint8_t* out, size_t cap,
-                       size_t* len) {
+                       size_t* len, int ew = 0, int eh = 0) {
   JpgGeom g;
-  if (quality < 1 || quality > 100 || !jpg_geom(d->g.W, d->g.H, sampling, &g) || ((uintptr_t)img & 7))
+  const int W = ew ? ew : d->g.W, H = eh ? eh : d->g.H;
+  if (W > d->g.W || H > d->g.H) return AT_E_INVALID;  // the buffers of jpeg_prepare bound it
+  if (quality < 1 || quality > 100 || !jpg_geom(W, H, sampling, &g) || ((uintptr_t)img & 7))
     return AT_E_INVALID;
   const int prc = jpeg_prepare(d);
   if (prc != AT_OK) return prc;
-  if (!d->jpg_hdr_len || d->jpg_hdr_q != quality || d->jpg_hdr_s != sampling) {
-    d->jpg_hdr_len = jpg_write_header(d->jpg_hdr, d->g.W, d->g.H, quality, sampling);
+  if (!d->jpg_hdr_len || d->jpg_hdr_q != quality || d->jpg_hdr_s != sampling || d->jpg_hdr_w != W ||
+      d->jpg_hdr_h != H) {
+    d->jpg_hdr_len = jpg_write_header(d->jpg_hdr, W, H, quality, sampling);
     d->jpg_hdr_q = quality;
     d->jpg_hdr_s = sampling;
+    d->jpg_hdr_w = W;
+    d->jpg_hdr_h = H;
   }
   d->jpg.row_words = (size_t)g.mcux * g.bpm * (kJpgBlockBytes / 4) + 4;
   const bool timed = d->profiling != 0;
@@ -1817,7 +1769,7 @@ static int encode_jpeg(at_detector* d, const uint8_t* img, int quality, int samp
       if (!e) HIPCHK(hipEventCreateWithFlags(&e, kTimingEventFlags));
     HIPCHK(hipEventRecord(d->ev_jpg[0], d->st));
   }
-  HIPCHK(launch_jpg_encode(img, d->g.W, d->g.H, quality, sampling, d->jpg, d->st));
+  HIPCHK(launch_jpg_encode(img, W, H, quality, sampling, d->jpg, d->st));
   if (timed) HIPCHK(hipEventRecord(d->ev_jpg[1], d->st));
   HIPCHK(hipStreamSynchronize(d->st));
   const size_t body = *(volatile uint32_t*)d->h_jpg_total;
@@ -1873,7 +1825,7 @@ int at_gp_annotate_jpeg(at_detector* d, int frame, const at_gp_box* boxes, int n
   int rc = gp_staged_image(d, frame, &img);
   if (rc != AT_OK) return rc;
   std::vector<DrawPrim> prims;
-  box_prims(d, boxes, n, &prims);
+  box_prims(d->g.W, d->g.H, boxes, n, &prims);
   rc = draw_prims(d, prims, img);
   if (rc != AT_OK) return rc;
   return encode_jpeg(d, img, quality, sampling, out, cap, len);
@@ -1883,6 +1835,143 @@ int at_jpeg_stats(at_detector* d, uint64_t* out, int cap) {
   if (!d || !out || cap < 1) return AT_E_INVALID;
   const int n = std::min(cap, 2);
   for (int i = 0; i < n; i++) out[i] = d->jpg_stats[i];
+  return n;
+}
+
+// ---- preview stream -------------------------------------------------------------
+// k_preview turns a staged frame of any format into the pw x ph BGR8 image d_pv (the source
+// is only read), the existing draw and encode kernels run on it at that geometry, and a
+// bounded quality search (preview_budget_search, shared with the CPU reference) keeps the
+// stream under a byte budget.  On the detector's stream, outside the captured graphs.
+
+// the frame a host-fed batch staged: any format, MJPG with or without colour
+static int preview_source(at_detector* d, int frame, const uint8_t** src, int* fmt) {
+  if (!d->last_staged || frame < 0 || frame >= d->last_nframes) return AT_E_INVALID;
+  HIPCHK(hipSetDevice(d->device));
+  if (d->pending) HIPCHK(hipEventSynchronize(d->ev_done));
+  // a colour MJPG batch: the decoded image; a luma-only one: the gray plane in the frame's slot
+  *src = (d->last_mj_color ? d->d_mj_bgr : d->d_in) + (size_t)frame * d->in_stride;
+  *fmt = d->last_mj_color ? (int)AT_FMT_BGR8 : d->last_fmt;
+  return AT_OK;
+}
+
+// d_pv = the annotated preview of `src`, queued on the detector's stream (not waited for)
+static int preview_draw(at_detector* d, const uint8_t* src, int fmt, const PvGeom& g, const at_detection* dets, int n,
+                        const at_gp_box* boxes, int nb) {
+  if (!d->d_pv) HIPCHK(hipMalloc((void**)&d->d_pv, (size_t)d->g.W * d->g.H * 3));
+  memset(d->pv_stats, 0, sizeof(d->pv_stats));
+  d->pv_stats[3] = (uint64_t)g.pw;
+  d->pv_stats[4] = (uint64_t)g.ph;
+  const bool timed = d->profiling != 0;
+  if (timed) {
+    for (hipEvent_t& e : d->ev_pv)
+      if (!e) HIPCHK(hipEventCreateWithFlags(&e, kTimingEventFlags));
+    HIPCHK(hipEventRecord(d->ev_pv[0], d->st));
+  }
+  HIPCHK(launch_preview(src, fmt, g.W, g.H, g.s, d->d_pv, d->st));
+  std::vector<DrawPrim> prims;
+  preview_prims(g, dets, n, boxes, nb, &prims);
+  const int rc = draw_prims(d, prims, d->d_pv, g.pw, g.ph);
+  if (rc != AT_OK) return rc;
+  if (timed) HIPCHK(hipEventRecord(d->ev_pv[1], d->st));
+  return AT_OK;
+}
+
+// after the stream was waited for: the time of k_preview and the drawing
+static int preview_time(at_detector* d) {
+  if (!d->profiling) return AT_OK;
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, d->ev_pv[0], d->ev_pv[1]));
+  d->pv_stats[5] += (uint64_t)((double)ms * 1e6);
+  return AT_OK;
+}
+
+static bool preview_args_ok(const at_detector* d, const at_detection* dets, int n, const at_gp_box* boxes, int nb) {
+  return d && n >= 0 && (n == 0 || dets) && nb >= 0 && (nb == 0 || boxes);
+}
+
+int at_preview_bgr(at_detector* d, int frame, int scale, const at_detection* dets, int n, const at_gp_box* boxes,
+                   int nb, uint8_t* bgr_out) {
+  PvGeom g;
+  if (!preview_args_ok(d, dets, n, boxes, nb) || !bgr_out || !pv_geom(d->g.W, d->g.H, scale, &g)) return AT_E_INVALID;
+  const uint8_t* src = nullptr;
+  int fmt = 0;
+  int rc = preview_source(d, frame, &src, &fmt);
+  if (rc != AT_OK) return rc;
+  rc = preview_draw(d, src, fmt, g, dets, n, boxes, nb);
+  if (rc != AT_OK) return rc;
+  const size_t bytes = (size_t)g.pw * g.ph * 3;
+  HIPCHK(hipMemcpyAsync(bgr_out, d->d_pv, bytes, hipMemcpyDeviceToHost, d->st));
+  HIPCHK(hipStreamSynchronize(d->st));
+  d->pv_stats[0] = bytes;
+  return preview_time(d);
+}
+
+// the encode (with the budget search) of the preview of `src`
+static int preview_jpeg(at_detector* d, const uint8_t* src, int fmt, const PvGeom& g, const at_detection* dets, int n,
+                        const at_gp_box* boxes, int nb, int quality, int sampling, size_t max_bytes, uint8_t* out,
+                        size_t cap, size_t* len, int* quality_used) {
+  int rc = preview_draw(d, src, fmt, g, dets, n, boxes, nb);
+  if (rc != AT_OK) return rc;
+  uint64_t enc_ns = 0;
+  int qu = 0, encodes = 0;
+  rc = preview_budget_search(
+      quality, max_bytes, cap,
+      [&](int q, size_t limit, size_t* l) {
+        const int e = encode_jpeg(d, d->d_pv, q, sampling, out, limit, l, g.pw, g.ph);
+        enc_ns += d->jpg_stats[1];
+        return e;
+      },
+      len, &qu, &encodes);
+  if (quality_used) *quality_used = qu;
+  d->pv_stats[0] = *len;
+  d->pv_stats[1] = (uint64_t)qu;
+  d->pv_stats[2] = (uint64_t)encodes;
+  if (rc != AT_OK && rc != AT_E_CAPACITY) return rc;
+  const int trc = preview_time(d);  // (every encode waited for the stream)
+  d->pv_stats[5] += enc_ns;
+  return trc != AT_OK ? trc : rc;
+}
+
+static bool preview_jpeg_args_ok(const PvGeom& g, int quality, int sampling, const uint8_t* out, const size_t* len) {
+  JpgGeom jg;
+  return out && len && quality >= 1 && quality <= 100 && jpg_geom(g.pw, g.ph, sampling, &jg);
+}
+
+int at_preview_jpeg(at_detector* d, int frame, int scale, const at_detection* dets, int n, const at_gp_box* boxes,
+                    int nb, int quality, int sampling, size_t max_bytes, uint8_t* out, size_t cap, size_t* len,
+                    int* quality_used) {
+  if (len) *len = 0;
+  if (quality_used) *quality_used = 0;
+  PvGeom g;
+  if (!preview_args_ok(d, dets, n, boxes, nb) || !pv_geom(d->g.W, d->g.H, scale, &g) ||
+      !preview_jpeg_args_ok(g, quality, sampling, out, len))
+    return AT_E_INVALID;
+  const uint8_t* src = nullptr;
+  int fmt = 0;
+  const int rc = preview_source(d, frame, &src, &fmt);
+  if (rc != AT_OK) return rc;
+  return preview_jpeg(d, src, fmt, g, dets, n, boxes, nb, quality, sampling, max_bytes, out, cap, len, quality_used);
+}
+
+int at_preview_jpeg_device(at_detector* d, const void* d_frame, at_pixfmt fmt, int scale, const at_detection* dets,
+                           int n, const at_gp_box* boxes, int nb, int quality, int sampling, size_t max_bytes,
+                           uint8_t* out, size_t cap, size_t* len, int* quality_used) {
+  if (len) *len = 0;
+  if (quality_used) *quality_used = 0;
+  PvGeom g;
+  if (!preview_args_ok(d, dets, n, boxes, nb) || !d_frame || ((uintptr_t)d_frame & 7) || !check_fmt(fmt) ||
+      !pv_geom(d->g.W, d->g.H, scale, &g) || !preview_jpeg_args_ok(g, quality, sampling, out, len))
+    return AT_E_INVALID;
+  HIPCHK(hipSetDevice(d->device));
+  return preview_jpeg(d, (const uint8_t*)d_frame, fmt, g, dets, n, boxes, nb, quality, sampling, max_bytes, out, cap,
+                      len, quality_used);
+}
+
+int at_preview_stats(at_detector* d, uint64_t* out, int cap) {
+  if (!d || !out || cap < 1) return AT_E_INVALID;
+  const int n = std::min(cap, 6);
+  for (int i = 0; i < n; i++) out[i] = d->pv_stats[i];
   return n;
 }
 

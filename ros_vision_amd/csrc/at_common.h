@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "at_detmath.h"
+#include "at_preview.h"
 
 namespace at {
 
@@ -267,11 +268,7 @@ struct QuadPend {
 };
 static_assert(sizeof(QuadPend) == 80, "QuadPend: 80 B per kept blob");
 
-// One 2-px-thick segment of the annotated image (at_draw_outlines_device).
-struct DrawPrim {
-  double x0, y0, x1, y1;
-  uint8_t bgr[3];
-};
+// (DrawPrim, one 2-px-thick segment of the annotated image: at_preview.h)
 
 // Buffers of the JPEG output (at_encode_jpeg_device), sized for 4:4:4 at the detector's
 // geometry; rows = MCU rows, each one restart interval.

@@ -6062,24 +6062,7 @@ hipError_t launch_gp_preprocess(const uint8_t* src, int w, int h, float* out, in
 // record (the scratch plane stays zero between calls).  Same double arithmetic as
 // the CPU code (no contraction): the images are bit-identical.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ bool seg_box(const DrawPrim& q, int W, int H, int* x0, int* y0, int* bw, int* bh) {
-  const double r = 1.0;  // thickness 2 / 2
-  const int xa = (int)floor(fmin(q.x0, q.x1) - r), xb = (int)ceil(fmax(q.x0, q.x1) + r);
-  const int ya = (int)floor(fmin(q.y0, q.y1) - r), yb = (int)ceil(fmax(q.y0, q.y1) + r);
-  *x0 = max(xa, 0);
-  *y0 = max(ya, 0);
-  *bw = min(xb, W - 1) - *x0 + 1;
-  *bh = min(yb, H - 1) - *y0 + 1;
-  return *bw > 0 && *bh > 0;
-}
-__device__ __forceinline__ bool seg_covers(const DrawPrim& q, int x, int y) {
-  const double r = 1.0;
-  const double dx = q.x1 - q.x0, dy = q.y1 - q.y0, l2 = dx * dx + dy * dy;
-  double u = l2 > 0 ? ((x - q.x0) * dx + (y - q.y0) * dy) / l2 : 0.0;
-  u = fmin(1.0, fmax(0.0, u));
-  const double ex = q.x0 + u * dx - x, ey = q.y0 + u * dy - y;
-  return ex * ex + ey * ey <= r * r;
-}
+// (seg_box / seg_covers: at_preview.h, shared with the CPU drawing of at_preview_host)
 template <bool PAINT>
 __global__ __launch_bounds__(256) void k_draw(const DrawPrim* prims, uint32_t* last, uint8_t* bgr, int W, int H) {
   const int p = blockIdx.x;
@@ -6105,6 +6088,110 @@ hipError_t launch_draw(const DrawPrim* prims, int n, uint32_t* last, uint8_t* bg
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_draw<false>, dim3(n), dim3(256), 0, st, prims, last, bgr, W, H);
   hipLaunchKernelGGL(k_draw<true>, dim3(n), dim3(256), 0, st, prims, last, bgr, W, H);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Preview (at_preview_bgr / at_preview_jpeg): a staged frame of any input format to a
+// pw x ph BGR8 image, each pixel the rounded mean of its s x s box of converted source
+// pixels (at_preview.h has the definition and the arithmetic; at_preview_host is the CPU
+// reference).  A pure streaming read of the crop; the source is not written.
+//
+// One thread per preview pixel, 64 x 4 per workgroup, so a wave reads one contiguous
+// stretch of 64 * s source pixels per row.  Per source row a thread needs n bytes from
+// byte a of the row (BGR8 3 s, GRAY8 s, YUYV the whole pairs that hold its s pixels).
+// Rows start 8-byte aligned and are a multiple of 8 bytes long (W % 8 == 0, the frame
+// 8-byte aligned), so the thread reads the aligned 8-byte units that hold [a, a + n) --
+// never one that ends beyond the row -- and shifts them down by a % 8 (a dword select and
+// a 64-bit funnel shift) into words whose bytes then have compile-time positions: no
+// byte loads, no dynamically indexed array, no scratch, no LDS, no atomics.
+// Instantiated per (format, s); s and the format are uniform over the launch.
+// ---------------------------------------------------------------------------
+template <int FMT, int S>
+__global__ __launch_bounds__(256) void k_preview(const uint8_t* __restrict__ src, int W, int ox, int oy, int pw, int ph,
+                                                 uint8_t* __restrict__ dst) {
+  constexpr int BPP = FMT == kPvBgr8 ? 3 : (FMT == kPvYuyv ? 2 : 1);
+  constexpr int NMAX = FMT == kPvYuyv ? 2 * S + 4 : S * BPP;  // most bytes of a row one thread needs
+  constexpr int NAL = (NMAX + 3) / 4;                        // ... as words from its first byte
+  constexpr int NU = (NAL + 3) / 2;                          // 8-byte units that can hold them: 2 NU >= NAL + 2
+  const int px = blockIdx.x * 64 + threadIdx.x, py = blockIdx.y * 4 + threadIdx.y;
+  if (px >= pw || py >= ph) return;
+  const int x0 = ox + px * S;
+  const int odd = FMT == kPvYuyv ? (x0 & 1) : 0;  // the first pixel is the second of its pair
+  const size_t a = (size_t)(x0 - odd) * BPP;
+  const int n = FMT == kPvYuyv ? 2 * ((odd + S + 1) & ~1) : S * BPP;
+  const int sh = (int)(a & 7);
+  const int nu = (sh + n + 7) >> 3;  // units that intersect [a, a + n): nu <= NU
+  int sb = 0, sg = 0, sr = 0;
+#pragma unroll
+  for (int j = 0; j < S; j++) {
+    const uint2* row = (const uint2*)(src + (size_t)(oy + py * S + j) * W * BPP + (a & ~(size_t)7));
+    uint32_t d[2 * NU];
+#pragma unroll
+    for (int u = 0; u < NU; u++) {
+      const uint2 v = u < nu ? row[u] : make_uint2(0u, 0u);
+      d[2 * u] = v.x;
+      d[2 * u + 1] = v.y;
+    }
+    uint32_t al[NAL];  // al[k]: bytes a + 4 k .. a + 4 k + 3 of the row
+#pragma unroll
+    for (int k = 0; k < NAL; k++) {
+      const uint32_t lo = (sh & 4) ? d[k + 1] : d[k], hi = (sh & 4) ? d[k + 2] : d[k + 1];
+      al[k] = (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * (sh & 3)));
+    }
+#define PV_BYTE(i) ((int)((al[(i) >> 2] >> (8 * ((i) & 3))) & 0xffu))
+#pragma unroll
+    for (int i = 0; i < S; i++) {
+      if (FMT == kPvBgr8) {
+        sb += PV_BYTE(3 * i);
+        sg += PV_BYTE(3 * i + 1);
+        sr += PV_BYTE(3 * i + 2);
+      } else if (FMT == kPvGray8) {
+        sb += PV_BYTE(i);
+      } else {
+        // pixel i is pixel i + odd of the pairs read
+        const int Y = odd ? PV_BYTE(2 * i + 2) : PV_BYTE(2 * i);
+        const int U = odd ? PV_BYTE(4 * ((i + 1) >> 1) + 1) : PV_BYTE(4 * (i >> 1) + 1);
+        const int V = odd ? PV_BYTE(4 * ((i + 1) >> 1) + 3) : PV_BYTE(4 * (i >> 1) + 3);
+        int b, g, r;
+        pv_yuyv_bgr(Y, U, V, &b, &g, &r);
+        sb += b;
+        sg += g;
+        sr += r;
+      }
+    }
+#undef PV_BYTE
+  }
+  uint8_t* o = dst + ((size_t)py * pw + px) * 3;
+  if (FMT == kPvGray8) {
+    o[0] = o[1] = o[2] = (uint8_t)pv_avg(sb, S);
+  } else {
+    o[0] = (uint8_t)pv_avg(sb, S);
+    o[1] = (uint8_t)pv_avg(sg, S);
+    o[2] = (uint8_t)pv_avg(sr, S);
+  }
+}
+
+template <int FMT>
+static void launch_preview_fmt(const uint8_t* src, const PvGeom& g, uint8_t* dst, hipStream_t st) {
+  const dim3 grid((g.pw + 63) / 64, (g.ph + 3) / 4), block(64, 4);
+#define PV_CASE(S_) \
+  case S_: hipLaunchKernelGGL((k_preview<FMT, S_>), grid, block, 0, st, src, g.W, g.ox, g.oy, g.pw, g.ph, dst); break;
+  switch (g.s) {
+    PV_CASE(1) PV_CASE(2) PV_CASE(3) PV_CASE(4) PV_CASE(5) PV_CASE(6) PV_CASE(7) PV_CASE(8)
+    default: break;
+  }
+#undef PV_CASE
+}
+
+// src: one frame of W x H in `fmt` (W % 8 == 0, 8-byte aligned); dst: pw x ph x 3
+hipError_t launch_preview(const uint8_t* src, int fmt, int W, int H, int s, uint8_t* dst, hipStream_t st) {
+  PvGeom g;
+  if (!pv_geom(W, H, s, &g) || (W & 7) || ((uintptr_t)src & 7)) return hipErrorInvalidValue;
+  if (fmt == kPvBgr8) launch_preview_fmt<kPvBgr8>(src, g, dst, st);
+  else if (fmt == kPvYuyv) launch_preview_fmt<kPvYuyv>(src, g, dst, st);
+  else if (fmt == kPvGray8) launch_preview_fmt<kPvGray8>(src, g, dst, st);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

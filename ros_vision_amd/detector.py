@@ -42,6 +42,8 @@ EXPORTS = [
     "at_gp_parse_host", "at_gp_parse_device", "at_gp_draw_boxes_device", "at_gp_parse_stats",
     "at_gp_annotate_staged", "at_gp_annotate_jpeg", "at_gp_copy_raw",
     "at_mjpg_set_device_entropy", "at_mjpg_set_subseq", "at_mjpg_entropy_host", "at_mjpg_dense_host",
+    "at_preview_size", "at_preview_bgr", "at_preview_jpeg", "at_preview_jpeg_device", "at_preview_host",
+    "at_preview_jpeg_host", "at_preview_stats",
 ]
 AT_GP_MAX_CANDIDATES = 4096
 # at_gp_box as a numpy record (the bit-exact view of what the library wrote)
@@ -257,6 +259,17 @@ def load_library(path: str = LIB_PATH):
         L.at_gp_annotate_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.c_size_t, C.POINTER(C.c_size_t)]
         L.at_gp_copy_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    if hasattr(L, "at_preview_jpeg"):  # (A/B builds of older sources lack the preview stream)
+        ip = C.POINTER(C.c_int)
+        recs = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]  # at_detection records, boxes
+        jpeg_tail = [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), ip]
+        L.at_preview_size.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]
+        L.at_preview_bgr.argtypes = [C.c_void_p, C.c_int, C.c_int] + recs + [C.c_void_p]
+        L.at_preview_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_int] + recs + jpeg_tail
+        L.at_preview_jpeg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + recs + jpeg_tail
+        L.at_preview_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + recs + [C.c_void_p, C.c_size_t]
+        L.at_preview_jpeg_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + recs + jpeg_tail
+        L.at_preview_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
     _LIB = L
     return L
 
@@ -342,6 +355,99 @@ def jpeg_encode_host(bgr, quality=95, sampling="4:2:0", cap=None):
     if rc < 0:
         raise JpegError("at_jpeg_encode_host", rc, n.value)
     return out[:n.value].tobytes()
+
+
+def preview_size(width: int, height: int, scale: int):
+    """at_preview_size: (pw, ph, ox, oy) of the preview of a width x height frame at integer
+    `scale` 1..8 -- pw = (width // scale) & ~7, the crop centred.  JpegError (AT_E_INVALID)
+    for a scale outside 1..8 or a preview under 8 x 8."""
+    v = [C.c_int() for _ in range(4)]
+    rc = load_library().at_preview_size(int(width), int(height), int(scale), *[C.byref(x) for x in v])
+    if rc < 0:
+        raise JpegError("at_preview_size", rc)
+    return tuple(x.value for x in v)
+
+
+def _box_records(boxes):
+    """GP_BOX_DTYPE records of GamePieceBox objects / records / None."""
+    if boxes is None:
+        return np.empty(0, GP_BOX_DTYPE)
+    if isinstance(boxes, np.ndarray) and boxes.dtype == GP_BOX_DTYPE:
+        return np.ascontiguousarray(boxes)
+    return np.array([(b.x, b.y, b.w, b.h, b.conf, b.cls) for b in boxes], GP_BOX_DTYPE)
+
+
+def _detection_records(dets):
+    """An AtDetection array of AtDetection records or Detection objects, and its length."""
+    dets = list(dets or ())
+    arr = (AtDetection * max(1, len(dets)))()
+    for i, d in enumerate(dets):
+        if isinstance(d, AtDetection):
+            arr[i] = d
+            continue
+        arr[i].id, arr[i].hamming, arr[i].decision_margin = int(d.id), int(d.hamming), float(d.decision_margin)
+        for k, v in enumerate(np.asarray(d.H, np.float64).reshape(9)):
+            arr[i].H[k] = v
+        arr[i].c[0], arr[i].c[1] = float(d.c[0]), float(d.c[1])
+        for k in range(4):
+            arr[i].p[k][0], arr[i].p[k][1] = float(d.p[k][0]), float(d.p[k][1])
+    return arr, len(dets)
+
+
+def _preview_frame(frame, fmt):
+    """(contiguous uint8 frame, width, height) of a frame shaped as the detector takes it."""
+    frame = np.ascontiguousarray(frame, np.uint8)
+    h = frame.shape[0]
+    if fmt == AT_FMT_BGR8:
+        w = frame.shape[1]
+    elif fmt == AT_FMT_YUYV:
+        w = frame.shape[1] if frame.ndim == 3 else frame.shape[1] // 2
+    else:
+        w = frame.shape[1]
+    return frame, w, h
+
+
+def preview_host(frame, fmt, scale, detections=None, boxes=None):
+    """at_preview_host: the CPU reference of GpuDetector.preview_bgr (no device needed).
+    `frame`: (H, W, 3) BGR8, (H, W, 2) or (H, 2 W) YUYV, (H, W) GRAY8; `detections`:
+    Detection objects or at_detection records; `boxes`: GamePieceBox objects or records.
+    Returns the annotated preview (ph, pw, 3) uint8."""
+    L = load_library()
+    frame, w, h = _preview_frame(frame, fmt)
+    pw, ph, _, _ = preview_size(w, h, scale)
+    arr, n = _detection_records(detections)
+    rec = _box_records(boxes)
+    out = np.empty((ph, pw, 3), np.uint8)
+    rc = L.at_preview_host(frame.ctypes.data, fmt, w, h, int(scale), C.addressof(arr), n,
+                           rec.ctypes.data if len(rec) else None, len(rec), out.ctypes.data, out.size)
+    if rc < 0:
+        raise JpegError("at_preview_host", rc)
+    return out
+
+
+def preview_jpeg_host(frame, fmt, scale, detections=None, boxes=None, quality=50, sampling="4:2:0", max_bytes=0,
+                      cap=None):
+    """at_preview_jpeg_host: the CPU reference of GpuDetector.preview_jpeg: (bytes, quality
+    used).  JpegError with code AT_E_CAPACITY, `needed` and `quality_used` when the stream
+    exceeds `cap` or no quality fits `max_bytes`."""
+    L = load_library()
+    frame, w, h = _preview_frame(frame, fmt)
+    pw, ph, _, _ = preview_size(w, h, scale)
+    s = _jpeg_sampling(sampling)
+    if cap is None:
+        cap = int(L.at_jpeg_max_bytes(pw, ph, s))
+    arr, n = _detection_records(detections)
+    rec = _box_records(boxes)
+    out = np.empty(max(int(cap), 1), np.uint8)
+    ln, qu = C.c_size_t(), C.c_int()
+    rc = L.at_preview_jpeg_host(frame.ctypes.data, fmt, w, h, int(scale), C.addressof(arr), n,
+                                rec.ctypes.data if len(rec) else None, len(rec), int(quality), s, int(max_bytes),
+                                out.ctypes.data, int(cap), C.byref(ln), C.byref(qu))
+    if rc < 0:
+        e = JpegError("at_preview_jpeg_host", rc, ln.value)
+        e.quality_used = qu.value
+        raise e
+    return out[:ln.value].tobytes(), qu.value
 
 
 def mjpg_stream_mode(jpg: bytes, width: int = 0, height: int = 0):
@@ -882,6 +988,81 @@ class GpuDetector:
         buf = (C.c_uint64 * len(self.JPEG_STATS))()
         n = _check(load_library().at_jpeg_stats(self._h, buf, len(buf)), "at_jpeg_stats")
         return dict(zip(self.JPEG_STATS, [int(x) for x in buf[:n]]))
+
+    # ---- the preview stream: a scaled annotated image of a frame of any format ----
+    def preview_size(self, scale: int):
+        """(pw, ph, ox, oy) of this detector's preview at `scale` (see preview_size)."""
+        return preview_size(self.width, self.height, scale)
+
+    def _preview_records(self, frame, detections, boxes):
+        if detections is None:  # the frame's own (a frame index no batch can have: the library refuses it)
+            arr, nd = self._records_array(frame) if 0 <= frame < self.max_batch and frame < len(self._n) else \
+                ((AtDetection * 1)(), 0)
+        else:
+            arr, nd = _detection_records(detections)
+        return arr, nd, _box_records(boxes)
+
+    def preview_bgr(self, frame=0, scale=4, boxes=None, detections=None):
+        """at_preview_bgr: the annotated preview (ph, pw, 3) uint8 of frame `frame` of the last
+        host-fed batch, whatever its format (BGR8, YUYV, GRAY8, MJPG with or without colour):
+        converted and box-averaged by k_preview from the staged frame, which is only read;
+        the frame's detections (or `detections`) and `boxes` are drawn at preview scale."""
+        pw, ph, _, _ = self.preview_size(scale)
+        arr, nd, rec = self._preview_records(frame, detections, boxes)
+        out = np.empty((ph, pw, 3), np.uint8)
+        rc = load_library().at_preview_bgr(self._h, frame, int(scale), C.addressof(arr), nd,
+                                           rec.ctypes.data if len(rec) else None, len(rec), out.ctypes.data)
+        if rc == AT_E_INVALID:
+            raise JpegError("at_preview_bgr", rc)
+        _check(rc, "at_preview_bgr")
+        return out
+
+    def _preview_jpeg_result(self, rc, what, n, qu):
+        if rc in (AT_E_INVALID, AT_E_CAPACITY):
+            e = JpegError(what, rc, n.value)
+            e.quality_used = qu.value
+            raise e
+        _check(rc, what)
+        return C.string_at(self._jpeg_buf, n.value), qu.value
+
+    def preview_jpeg(self, frame=0, scale=4, quality=50, sampling="4:2:0", max_bytes=0, boxes=None, detections=None,
+                     cap=None):
+        """at_preview_jpeg: preview_bgr's image as a baseline JPEG: (bytes, quality used).
+        `max_bytes` > 0 is the frame's byte budget: the quality is lowered by the bounded
+        bisection of at_api.h until the stream fits (JpegError AT_E_CAPACITY, `needed` and
+        `quality_used` == 1 if quality 1 does not)."""
+        if not 1 <= int(scale) <= 8:
+            raise JpegError("at_preview_jpeg", AT_E_INVALID)
+        arr, nd, rec = self._preview_records(frame, detections, boxes)
+        s, cap = self._jpeg_out(sampling, cap)
+        n, qu = C.c_size_t(), C.c_int()
+        rc = load_library().at_preview_jpeg(self._h, frame, int(scale), C.addressof(arr), nd,
+                                            rec.ctypes.data if len(rec) else None, len(rec), int(quality), s,
+                                            int(max_bytes), self._jpeg_buf, cap, C.byref(n), C.byref(qu))
+        return self._preview_jpeg_result(rc, "at_preview_jpeg", n, qu)
+
+    def preview_jpeg_device(self, dev_ptr: int, fmt: int, scale=4, quality=50, sampling="4:2:0", max_bytes=0,
+                            boxes=None, detections=(), cap=None):
+        """at_preview_jpeg_device: the same for one device-resident frame of the detector's
+        geometry in `fmt` at `dev_ptr` (8-byte aligned), e.g. a frame of an enqueue_device
+        batch; `detections` are drawn as given."""
+        arr, nd = _detection_records(detections)
+        rec = _box_records(boxes)
+        s, cap = self._jpeg_out(sampling, cap)
+        n, qu = C.c_size_t(), C.c_int()
+        rc = load_library().at_preview_jpeg_device(self._h, C.c_void_p(dev_ptr), int(fmt), int(scale),
+                                                   C.addressof(arr), nd, rec.ctypes.data if len(rec) else None,
+                                                   len(rec), int(quality), s, int(max_bytes), self._jpeg_buf, cap,
+                                                   C.byref(n), C.byref(qu))
+        return self._preview_jpeg_result(rc, "at_preview_jpeg_device", n, qu)
+
+    PREVIEW_STATS = ("bytes", "quality_used", "encodes", "width", "height", "kernels_ns")
+
+    def preview_stats(self):
+        """at_preview_stats of the last preview call."""
+        buf = (C.c_uint64 * len(self.PREVIEW_STATS))()
+        n = _check(load_library().at_preview_stats(self._h, buf, len(buf)), "at_preview_stats")
+        return dict(zip(self.PREVIEW_STATS, [int(x) for x in buf[:n]]))
 
     def frame_status(self, frame=0):
         return load_library().at_frame_status(self._h, frame)

@@ -126,6 +126,18 @@ class GamePieceResult:
     boxes: list = field(default_factory=list)     # [GamePieceBox], class_name filled in
     image: np.ndarray = None
     image_jpeg: bytes = None
+    preview_jpeg: bytes = None                    # preview_scale > 0: the scaled image with the boxes, as JPEG
+
+
+def _preview_options(scale, quality, max_bytes):
+    scale, quality, max_bytes = int(scale), int(quality), int(max_bytes)
+    if not 0 <= scale <= 8:
+        raise ValueError("preview_scale is an integer 1..8 (0: no preview)")
+    if not 1 <= quality <= 100:
+        raise ValueError("preview_quality is a JPEG quality, 1..100")
+    if max_bytes < 0:
+        raise ValueError("preview_max_bytes is a byte budget per frame (0: none)")
+    return scale, quality, max_bytes
 
 
 class GamePieceDetectorNode:
@@ -141,10 +153,16 @@ class GamePieceDetectorNode:
     `infer` is the user's engine: it gets the network input, a float32 CUDA torch tensor
     [1, C, H, W] on the current torch stream, and returns the output [1, 4 + classes, P]
     as a float32 CUDA tensor (produced on that stream).  input = (width, height,
-    channels) of the model."""
+    channels) of the model.
+
+    preview_scale = 1..8 (0, the default: off): the frame scaled down by that factor with the
+    boxes drawn at preview scale, JPEG-encoded on the GPU at preview_quality (lowered until the
+    stream fits preview_max_bytes, if that is set; a frame nothing fits has no preview), is
+    published on `<publish_to_topic>/preview/compressed` (at_preview_jpeg_device)."""
 
     def __init__(self, width, height, infer, input=(640, 640, 3), class_names=(), conf=0.25, iou=0.45,  # noqa: A002
-                 image_jpeg=None, parameters=None, publishers=None, device=0):
+                 image_jpeg=None, parameters=None, publishers=None, device=0, preview_scale=0, preview_quality=50,
+                 preview_max_bytes=0):
         import torch
         self._torch = torch
         self.params = dict(GAME_PIECE_PARAMETER_DEFAULTS)
@@ -160,6 +178,9 @@ class GamePieceDetectorNode:
         self.publishers = publishers or {}
         self.image_topic = self.params["publish_to_topic"]
         self.compressed_image_topic = self.image_topic + "/compressed"
+        self.preview_scale, self.preview_quality, self.preview_max_bytes = _preview_options(
+            preview_scale, preview_quality, preview_max_bytes)
+        self.preview_topic = self.image_topic + "/preview/compressed"
         self.detections_topic = self.image_topic.rsplit("/", 1)[0] + "/detections"
         self.device = torch.device("cuda", int(device))
         self.detector = GpuDetector(self.width, self.height, device=device, tag_size=0.0)
@@ -190,6 +211,11 @@ class GamePieceDetectorNode:
         rec = self.detector.game_piece_parse(raw, self.conf, self.iou, (self.input_width, self.input_height),
                                              producer_stream=stream, records=True)[0]
         res = GamePieceResult(boxes=game_piece_boxes(rec, self.class_names or ()))
+        if self.preview_scale:
+            # (before the boxes are drawn on the frame itself; the parse waited for `stream`)
+            res.preview_jpeg = _preview_or_none(lambda: self.detector.preview_jpeg_device(
+                self._frame.data_ptr(), AT_FMT_BGR8, self.preview_scale, quality=self.preview_quality,
+                max_bytes=self.preview_max_bytes, boxes=rec))
         want_raw, want_jpeg = self.image_topic in self.publishers, self.compressed_image_topic in self.publishers
         if (self.image_jpeg is None and want_raw) or (self.image_jpeg is not None and want_jpeg):
             # (the parse waited for `stream`: the preprocessing is done with the frame it now draws on)
@@ -204,7 +230,20 @@ class GamePieceDetectorNode:
             self._publish(self.image_topic, res.image)
         if res.image_jpeg is not None:
             self._publish(self.compressed_image_topic, res.image_jpeg)
+        if res.preview_jpeg is not None:
+            self._publish(self.preview_topic, res.preview_jpeg)
         return res
+
+
+def _preview_or_none(call):
+    """The preview's bytes; None for a frame whose preview fits the byte budget at no quality."""
+    from .detector import AT_E_CAPACITY, JpegError
+    try:
+        return call()[0]
+    except JpegError as e:
+        if e.code != AT_E_CAPACITY:
+            raise
+        return None
 
 
 @dataclass
@@ -216,13 +255,15 @@ class FrameResult:
     proto_tags: list = field(default_factory=list)                    # ApriltagListProto.tags
     image: np.ndarray = None
     image_jpeg: bytes = None                                          # image_jpeg set: the image as JPEG instead
+    preview_jpeg: bytes = None                                        # preview_scale > 0: the scaled annotated JPEG
 
 
 class ApriltagsDetectorNode:
     """ApriltagsDetector (apriltags_cuda_detector.cu) without the ROS transport."""
 
     def __init__(self, width, height, parameters=None, calibration_dir=None, system_config_path=None,
-                 publishers=None, device=0, mjpg_color=False, image_jpeg=None, mjpg_device_entropy=False):
+                 publishers=None, device=0, mjpg_color=False, image_jpeg=None, mjpg_device_entropy=False,
+                 preview_scale=0, preview_quality=50, preview_max_bytes=0):
         self.params = dict(PARAMETER_DEFAULTS)
         self.params.update(parameters or {})
         serial = self.params["camera_serial"]
@@ -254,6 +295,12 @@ class ApriltagsDetectorNode:
         if self.image_jpeg is not None and not 1 <= self.image_jpeg <= 100:
             raise ValueError("image_jpeg is a JPEG quality, 1..100")
         self.compressed_image_topic = self.image_topic + "/compressed"
+        # preview_scale = 1..8 (0: off): the frame of ANY encoding scaled down by that factor on the
+        # GPU, annotated at preview scale and JPEG-encoded at preview_quality -- lowered until the
+        # stream fits preview_max_bytes, if set -- on <publish_images_to_topic>/preview/compressed
+        self.preview_scale, self.preview_quality, self.preview_max_bytes = _preview_options(
+            preview_scale, preview_quality, preview_max_bytes)
+        self.preview_topic = self.image_topic + "/preview/compressed"
         self.csv = None
         if self.params["measurement_mode"]:
             path = self.params["timing_csv_path"] or time.strftime("apriltags_timing_%Y%m%d_%H%M%S.csv")
@@ -280,7 +327,9 @@ class ApriltagsDetectorNode:
         image is published for it only with mjpg_color=True: the frame's colour is then
         decoded on the GPU too and outlined there (at_annotate_staged); otherwise there is
         no colour image to draw on.  With image_jpeg set, whichever image there is goes out
-        as JPEG bytes on `<publish_images_to_topic>/compressed` and the raw topic is silent."""
+        as JPEG bytes on `<publish_images_to_topic>/compressed` and the raw topic is silent.
+        With preview_scale > 0 every encoding -- yuyv, mono8 and jpeg without colour included --
+        also gets the scaled annotated JPEG on `<publish_images_to_topic>/preview/compressed`."""
         start = time.perf_counter()
         latency_s = (receive_time_s if receive_time_s is not None else time.time()) - stamp_s
         det0 = time.perf_counter()
@@ -298,6 +347,10 @@ class ApriltagsDetectorNode:
             res.proto_tags.append({"collect_time": stamp_s, "tag_id": tag.id, "x": rx, "y": ry, "z": rz})
             res.tag_detection_camera_array.append((tag.id, *(float(v) for v in tag.camera)))
             res.tag_detection_array.append((tag.id, rx, ry, rz))
+        if self.preview_scale:
+            # (first: at_annotate_staged / at_annotate_jpeg below draw on the staged frame itself)
+            res.preview_jpeg = _preview_or_none(lambda: self.detector.preview_jpeg(
+                0, self.preview_scale, quality=self.preview_quality, max_bytes=self.preview_max_bytes))
         has_image = encoding == "bgr8" or (encoding == "jpeg" and self.mjpg_color)
         if has_image and self.image_jpeg is not None:
             res.image_jpeg = self.detector.annotate_jpeg(0, quality=self.image_jpeg, sampling="4:2:0")
@@ -317,6 +370,8 @@ class ApriltagsDetectorNode:
             self._publish(self.image_topic, res.image)
         if res.image_jpeg is not None:
             self._publish(self.compressed_image_topic, res.image_jpeg)
+        if res.preview_jpeg is not None:
+            self._publish(self.preview_topic, res.preview_jpeg)
         pi1 = time.perf_counter()
         if self.csv:
             us = lambda a, b: int(round((b - a) * 1e6))  # noqa: E731
