@@ -546,6 +546,62 @@ int at_preview_jpeg_host(const uint8_t *frame, at_pixfmt fmt, int w, int h, int 
                          uint8_t *out, size_t cap, size_t *len, int *quality_used);
 int at_preview_stats(at_detector *d, uint64_t *out, int cap);
 
+/* Field pose: one camera pose per frame from every tag of a known layout in it.
+ *
+ * k_pose gives each tag's own pose (four coplanar corners, the two-minimum ambiguity).  With
+ * a field layout set -- where each tag stands on the field, x_field = R x_tag + t, the tag
+ * frame being at_pose's: corners at (-+s/2, +-s/2, 0) in at_detection.p order, s = tag_size
+ * -- one more kernel (k_field, after k_pose in the launch sequence, like at_gp_enable's; gone
+ * again when the layout is cleared) solves per frame for the one camera pose that explains
+ * the corners of all its layout tags, and leaves it in mapped host memory: at_collect copies
+ * nothing more.
+ *
+ * Per frame:
+ *   select  the candidates (before reconcile) with an id of the layout and hamming <=
+ *           max_hamming; per id the lowest hamming, then the greatest decision_margin, then
+ *           the lowest candidate slot; the AT_FIELD_MAX_TAGS lowest ids;
+ *   points  each tag's corners in the field frame against at_detection.p through fx, fy,
+ *           cx, cy (p as k_pose reads it: no further undistortion);
+ *   start   each used tag's own pose as a camera pose, R_j = pose_R R_tag^T,
+ *           t_j = pose_t - R_j t_tag; the one with the least summed squared reprojection
+ *           error over all points (a point at Z <= 0: infinite; ties: the lower id);
+ *   refine  12 Levenberg-Marquardt iterations on the pixel residuals (6 parameters, rotation
+ *           update left-multiplied from q = (1, w / 2) normalised, damping lambda diag(J^T J)
+ *           from 1e-3, / 10 (floor 1e-9) on an accepted step, x 10 on a rejected one; a step
+ *           is accepted only if the cost falls and every Z stays positive).
+ * A frame without a layout tag (or whose tags' poses all put a point behind the camera) has
+ * n_tags = 0 and the rest zero.
+ *
+ * at_set_field_layout: n = 0 clears.  AT_E_INVALID: at_config.tag_size == 0, an id outside
+ * [0, 1024), an id twice, an R with |R R^T - I| above 1e-6 or det < 0, max_hamming < 0, a batch
+ * not yet collected.  It takes effect from the next enqueued batch.
+ * at_field_poses: one record per frame of the last collected batch (all n_tags = 0 if it ran
+ * without a layout); returns the frame count, writes at most cap.
+ * at_field_pose_host: the same solve on the CPU for one frame's at_detections / at_poses
+ * arrays (the CPU reference: it shares the kernel's arithmetic and takes the same
+ * accept / reject decisions); checks `tags` like at_set_field_layout.
+ * at_robot_in_field (host only): the robot's pose in the field, field_T_cam (robot_T_cam)^-1
+ * with the camera -> robot extrinsics of at_tag_detections (NULL = identity / zero):
+ * x_field = R_out x_robot + t_out.  AT_E_INVALID for a record with n_tags = 0.
+ * at_field_stats, the last collected batch: [0] frames solved, [1] tags used, [2] candidates
+ * dropped by the 16-tag cap, [3] rejected LM steps, [4] k_field's time in nanoseconds (HIP
+ * events; while at_set_profiling is on, 0 otherwise). */
+typedef struct { int32_t id; double R[9]; double t[3]; } at_field_tag;
+#define AT_FIELD_MAX_TAGS 16
+typedef struct {
+  int32_t n_tags;                   /* tags used; 0 = no layout tag in this frame (rest zeroed) */
+  int32_t ids[AT_FIELD_MAX_TAGS];   /* ascending */
+  double R[9]; double t[3];         /* x_cam = R x_field + t, row-major, like at_pose */
+  double rms_px;                    /* reprojection RMS over the 4*n_tags corners */
+  int32_t steps_taken;              /* accepted LM steps */
+} at_field_pose;
+int at_set_field_layout(at_detector *d, const at_field_tag *tags, int n, int max_hamming);
+int at_field_poses(at_detector *d, at_field_pose *out, int cap);
+int at_field_pose_host(const at_detection *dets, const at_pose *poses, int n, const at_field_tag *tags, int ntags,
+                       int max_hamming, const at_camera *cam, double tag_size, at_field_pose *out);
+int at_robot_in_field(const at_field_pose *fp, const double *extr_R, const double *extr_t, double *R_out, double *t_out);
+int at_field_stats(at_detector *d, uint64_t *out, int cap);
+
 /* Page-locked host memory (hipHostMalloc) for buffers the detector copies into on
  * its stream by DMA, e.g. at_annotate_staged's bgr_out: a pageable destination
  * goes through the runtime's staging buffers instead.  (No counterpart in the

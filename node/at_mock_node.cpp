@@ -20,6 +20,7 @@
 //        [--measurement-csv PATH] [--proto-out P] [--image-out I] [--device K] [--time N]
 //        [--mjpg-color] [--mjpg-device-entropy] [--jpeg-out DIR] [--jpeg-quality Q]
 //        [--preview-out DIR --preview-scale N [--preview-quality Q] [--preview-max-bytes B]]
+//        [--field-layout FILE [--field-max-hamming M]]
 //   As the reference node (apriltags_cuda_detector.cu:137-193): the frame size, the
 //   intrinsics and the extrinsics come from the camera serial's records in the
 //   vision_config_data share directory, found through $AMENT_PREFIX_PATH
@@ -30,6 +31,10 @@
 //   in turn (the whole callback: detect, poses, robot frame, messages, proto and, for
 //   bgr8, the outlined image drawn on the GPU and copied out), one JSON line with the
 //   p50 / p99 wall time per call instead of the per-frame lines.
+//   --field-layout FILE: where each tag stands on the field, one `id r00 .. r22 tx ty tz` per line
+//   (x_field = R x_tag + t; DetectorCore::set_field_layout).  Every frame's line gains "field":
+//   the camera pose from all its layout tags (n_tags, ids, R, t, rms_px, steps) and, when there is
+//   one, "robot_R" / "robot_t", the robot's pose in the field.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -92,7 +97,8 @@ std::vector<Span> split_mjpg(const std::vector<uint8_t>& d) {
 int main(int argc, char** argv) {
   int W = 0, H = 0, count = -1, device = 0, pin = -1, priority = 80, time_n = 0, jpeg_quality = 95;
   std::string fmt_s = "yuyv", frames_path, calib_dir, serial = "N/A", sys_cfg, csv, proto_out, image_out, share_dir;
-  std::string jpeg_out, preview_out;
+  std::string jpeg_out, preview_out, field_layout;
+  int field_max_hamming = 0;
   int preview_scale = 0, preview_quality = 50;
   long long preview_max_bytes = 0;
   bool mjpg_color = false, mjpg_device_entropy = false;
@@ -127,6 +133,8 @@ int main(int argc, char** argv) {
     else if (k == "--preview-scale") preview_scale = std::atoi(v.c_str());
     else if (k == "--preview-quality") preview_quality = std::atoi(v.c_str());
     else if (k == "--preview-max-bytes") preview_max_bytes = std::atoll(v.c_str());
+    else if (k == "--field-layout") field_layout = v;
+    else if (k == "--field-max-hamming") field_max_hamming = std::atoi(v.c_str());
     else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
   }
   at_node::Params prm;
@@ -207,6 +215,14 @@ int main(int argc, char** argv) {
       core.set_preview(preview_scale, preview_quality, (size_t)preview_max_bytes);
       ::mkdir(preview_out.c_str(), 0777);  // (exists already: fine)
     }
+    if (!field_layout.empty()) {
+      std::vector<at_field_tag> tags;
+      if (!at_node::load_field_layout(field_layout, &tags, &err)) {
+        std::fprintf(stderr, "field layout: %s\n", err.c_str());
+        return 1;
+      }
+      core.set_field_layout(tags, field_max_hamming);
+    }
     at_node::FrameOutputs out;
     at_node::ImageBuffer image;
     auto run = [&](int f, double stamp) {
@@ -270,10 +286,32 @@ int main(int argc, char** argv) {
         std::snprintf(buf, sizeof(buf), "%02x", c);
         hex += buf;
       }
+      std::string field;
+      if (!field_layout.empty()) {
+        auto nums = [&](const double* v, int n) {
+          std::string s = "[";
+          for (int i = 0; i < n; ++i) {
+            std::snprintf(buf, sizeof(buf), "%s%.17g", i ? "," : "", v[i]);
+            s += buf;
+          }
+          return s + "]";
+        };
+        std::string ids = "[";
+        for (int i = 0; i < out.field.n_tags; ++i) ids += (i ? "," : "") + std::to_string(out.field.ids[i]);
+        std::snprintf(buf, sizeof(buf), ",\"field_pose_topic\":\"%s\",\"field\":{\"n_tags\":%d,\"ids\":%s],",
+                      core.field_pose_topic().c_str(), out.field.n_tags, ids.c_str());
+        field = buf;
+        field += "\"R\":" + nums(out.field.R, 9) + ",\"t\":" + nums(out.field.t, 3);
+        std::snprintf(buf, sizeof(buf), ",\"rms_px\":%.17g,\"steps\":%d", out.field.rms_px, out.field.steps_taken);
+        field += buf;
+        if (out.have_robot_in_field)
+          field += ",\"robot_R\":" + nums(out.robot_field_R, 9) + ",\"robot_t\":" + nums(out.robot_field_t, 3);
+        field += "}";
+      }
       std::printf("{\"frame\":%d,\"status\":%d,\"location\":\"%s\",\"pose_topic\":\"%s\",\"camera_pose_topic\":\"%s\","
-                  "\"detections\":%s,\"robot\":%s,\"camera\":%s,\"networktables\":%s,\"proto_hex\":\"%s\"}\n",
+                  "\"detections\":%s,\"robot\":%s,\"camera\":%s,\"networktables\":%s,\"proto_hex\":\"%s\"%s}\n",
                   f, rc, location.c_str(), core.pose_topic().c_str(), core.camera_pose_topic().c_str(), dets.c_str(),
-                  sink.robot.c_str(), sink.camera.c_str(), nt.c_str(), hex.c_str());
+                  sink.robot.c_str(), sink.camera.c_str(), nt.c_str(), hex.c_str(), field.c_str());
       if (f == count - 1 && !proto_out.empty()) {
         std::ofstream po(proto_out, std::ios::binary);
         po.write(out.proto.data(), (std::streamsize)out.proto.size());

@@ -582,6 +582,41 @@ void DetectorCore::set_preview(int scale, int quality, size_t max_bytes) {
   preview_max_bytes_ = max_bytes;
 }
 
+void DetectorCore::set_field_layout(const std::vector<at_field_tag>& tags, int max_hamming) {
+  const int rc = at_set_field_layout(det_, tags.data(), (int)tags.size(), max_hamming);
+  if (rc != AT_OK) throw std::runtime_error(std::string("set_field_layout: ") + at_strerror(rc));
+  field_layout_ = !tags.empty();
+}
+
+bool load_field_layout(const std::string& path, std::vector<at_field_tag>* tags, std::string* err) {
+  tags->clear();
+  std::ifstream in(path);
+  if (!in) {
+    if (err) *err = "cannot read " + path;
+    return false;
+  }
+  std::string line;
+  for (int no = 1; std::getline(in, line); ++no) {
+    const size_t hash = line.find('#');
+    if (hash != std::string::npos) line.erase(hash);
+    if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+    std::istringstream ls(line);
+    at_field_tag g{};
+    double v[12];
+    bool ok = (bool)(ls >> g.id);
+    for (int k = 0; ok && k < 12; k++) ok = (bool)(ls >> v[k]);
+    std::string rest;
+    if (!ok || (ls >> rest)) {
+      if (err) *err = path + ":" + std::to_string(no) + ": expected `id r00 .. r22 tx ty tz`";
+      return false;
+    }
+    std::copy(v, v + 9, g.R);
+    std::copy(v + 9, v + 12, g.t);
+    tags->push_back(g);
+  }
+  return true;
+}
+
 // fmt < 0: `frame` is one MJPG frame of `len` bytes (at_detect_mjpg); the tail is the same
 int DetectorCore::run(const uint8_t* frame, size_t len, int fmt, double stamp_s, double receive_s, FrameOutputs* out,
                       ImageBuffer* annotate) {
@@ -612,6 +647,13 @@ int DetectorCore::run(const uint8_t* frame, size_t len, int fmt, double stamp_s,
     out->robot.push_back({d.id, d.robot[0], d.robot[1], d.robot[2]});
   }
   out->proto = encode_apriltag_list(out->tags.data(), (int)out->tags.size(), stamp_s);
+  if (field_layout_) {
+    // k_field left the frame's record in mapped host memory: nothing more to wait for
+    const int frc = at_field_poses(det_, &out->field, 1);
+    if (frc < 0) return frc;
+    out->have_robot_in_field =
+        out->field.n_tags > 0 && at_robot_in_field(&out->field, R_, t_, out->robot_field_R, out->robot_field_t) == AT_OK;
+  }
   if (preview_scale_) {
     // every format; first, since the annotation below is drawn on the staged frame itself
     const int prc = preview_encode(det_, preview_scale_, preview_quality_, preview_max_bytes_, out->detections.data(),
@@ -641,6 +683,8 @@ int DetectorCore::run(const uint8_t* frame, size_t len, int fmt, double stamp_s,
   if (publish_robot) publish_robot(ctx, out->robot);
   const auto pp1 = clk::now();
   if (publish_camera) publish_camera(ctx, out->camera);
+  if (publish_field_pose && out->have_robot_in_field)
+    publish_field_pose(ctx, out->robot_field_R, out->robot_field_t, out->field, stamp_s);
   const auto pc1 = clk::now();
   if (publish_image && annotate && !annotate->empty()) {
     if (!image_queue_) {

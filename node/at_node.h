@@ -93,7 +93,16 @@ struct FrameOutputs {
   int status = AT_OK;                             // at_detect return code
   int64_t det_time_us = 0;
   std::vector<uint8_t> preview_jpeg;              // set_preview: the scaled annotated JPEG (empty: none)
+  // set_field_layout: the frame's camera pose from all its layout tags (n_tags == 0: none in
+  // view) and, when there is one, the robot's pose in the field, x_field = R x_robot + t
+  at_field_pose field{};
+  bool have_robot_in_field = false;
+  double robot_field_R[9] = {0}, robot_field_t[3] = {0};
 };
+
+// A field layout as plain text: one tag per line, `id r00 r01 r02 r10 r11 r12 r20 r21 r22 tx ty tz`
+// (x_field = R x_tag + t; '#' starts a comment).  false and *err for a line that is not 13 numbers.
+bool load_field_layout(const std::string& path, std::vector<at_field_tag>* tags, std::string* err);
 
 // calibrationmatrix_<serial>.json: "matrix" 3x3 and "disto" [[k1 k2 p1 p2 k3]].
 bool load_camera_calibration(const std::string& dir, const std::string& serial, at_camera* cam, std::string* err);
@@ -272,6 +281,13 @@ class DetectorCore {
   void set_preview(int scale, int quality = 50, size_t max_bytes = 0);
   int preview_scale() const { return preview_scale_; }
   std::string preview_topic() const { return params_.publish_images_to_topic + "/preview/compressed"; }
+  // set_field_layout(tags, max_hamming): where each tag stands on the field (at_set_field_layout;
+  // an empty vector clears it; throws std::runtime_error for a layout the library refuses).  Every
+  // later frame's FrameOutputs::field is the camera pose the GPU solved from all its layout tags,
+  // and the robot's field pose (at_robot_in_field with the node's extrinsics) goes to
+  // publish_field_pose on field_pose_topic().
+  void set_field_layout(const std::vector<at_field_tag>& tags, int max_hamming = 0);
+  std::string field_pose_topic() const { return params_.publish_pose_to_topic + "/field"; }
 
   const Params& params() const { return params_; }
   int width() const { return width_; }
@@ -295,6 +311,9 @@ class DetectorCore {
   // ... with the preview's JPEG file (set_preview)
   void (*publish_preview)(void* ctx, const std::vector<uint8_t>&, double stamp_s) = nullptr;
   void (*send_networktables)(void* ctx, const std::vector<double>&, const std::string& proto) = nullptr;
+  // ... with the robot's pose in the field (set_field_layout; only for frames that have one)
+  void (*publish_field_pose)(void* ctx, const double R[9], const double t[3], const at_field_pose& field,
+                             double stamp_s) = nullptr;
   void* ctx = nullptr;
 
  private:
@@ -315,6 +334,7 @@ class DetectorCore {
   size_t preview_max_bytes_ = 0;
   ImageBuffer preview_buf_;  // page-locked, at_jpeg_max_bytes of the preview: allocated by set_preview
   std::unique_ptr<PublisherQueue<StampedImage>> preview_queue_;
+  bool field_layout_ = false;
   double R_[9], t_[3];
   at_detector* det_ = nullptr;
   std::vector<at_detection> dets_;

@@ -10,11 +10,13 @@ from .detector import (AT_FMT_BGR8, AT_FMT_GRAY8, AT_FMT_YUYV, TAG_SIZE, TEST_CA
                        mjpg_decode_bgr, mjpg_decode_gray, mjpg_dense_host, mjpg_entropy_host, mjpg_stream_mode,
                        tag_detections,
                        AT_GP_MAX_CANDIDATES, GP_BOX_DTYPE, GamePieceBox, GamePieceCapacityError, game_piece_boxes,
-                       game_piece_parse_host, preview_host, preview_jpeg_host, preview_size)
+                       game_piece_parse_host, preview_host, preview_jpeg_host, preview_size,
+                       FieldPose, FieldPoseError, field_pose_host, robot_in_field)
 
 __all__ = ["GpuDetector", "CameraMatrix", "DistCoeffs", "Detection", "Pose", "TagDetection", "load_library",
            "family_entries", "tag_detections", "game_piece_preprocess_device", "TAG_SIZE", "TEST_CAMERA", "TEST_DIST",
            "AT_FMT_YUYV", "AT_FMT_BGR8", "AT_FMT_GRAY8", "MjpgError", "mjpg_decode_gray", "mjpg_stream_mode",
            "mjpg_decode_bgr", "mjpg_dense_host", "mjpg_entropy_host", "JpegError", "jpeg_encode_host", "jpeg_max_bytes",
            "GamePieceBox", "GamePieceCapacityError", "game_piece_parse_host", "game_piece_boxes", "GP_BOX_DTYPE",
-           "AT_GP_MAX_CANDIDATES", "preview_size", "preview_host", "preview_jpeg_host"]
+           "AT_GP_MAX_CANDIDATES", "preview_size", "preview_host", "preview_jpeg_host",
+           "FieldPose", "FieldPoseError", "field_pose_host", "robot_in_field"]

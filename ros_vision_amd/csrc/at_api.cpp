@@ -46,7 +46,10 @@ hipError_t launch_gp_parse(const float* raw, size_t frame_stride, int nframes, i
 hipError_t prepare_kernels(const Geom& g);
 hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, int B, int fmt, int nblobwg,
                            hipStream_t st, hipEvent_t* ev, hipStream_t st2, hipEvent_t fork, hipEvent_t join,
-                           const KernelTimer* kt);
+                           const KernelTimer* kt, const FieldLaunch* field);
+// (at_fieldpose.cpp)
+int fp_build_layout(const at_field_tag* tags, int n, int16_t* lut, std::vector<FpTag>* out);
+void fp_write(const FpRecord& r, at_field_pose* o);
 
 struct CodeEntry {
   int id;
@@ -128,6 +131,7 @@ using namespace at;
 
 static_assert(kMjpgInvalid == AT_E_INVALID && kMjpgUnsupported == AT_E_UNSUPPORTED && kMjpgOk == AT_OK,
               "at_mjpg.h carries the ABI's codes");
+static_assert(kFpMaxIds == kMaxCodes && kMaxDets <= kFpMaxCand, "at_fieldpose.h: ids and candidate slots of a frame");
 static_assert(kJpg420 == AT_JPEG_420 && kJpg422 == AT_JPEG_422 && kJpg444 == AT_JPEG_444 && AT_E_CAPACITY == -3,
               "at_mjpg.h carries the ABI's sampling codes");
 
@@ -261,6 +265,15 @@ struct at_detector {
   uint8_t* d_pv;
   uint64_t pv_stats[6];     // last call: bytes, quality used, encodes, pw, ph, kernels' ns (while profiling)
   hipEvent_t ev_pv[2];      // around k_preview and the drawing (created on first use)
+  // field pose (at_set_field_layout): the layout in HBM (id table, tags; allocated on the first
+  // call at kMaxCodes entries and kept), one record per frame in HBM and in mapped host memory
+  FieldLaunch field;        // field.b: what k_field gets; field.ev: around it while stage profiling is on
+  int field_on;             // a layout is set: later batches run k_field
+  int last_field;           // the pending / last batch ran it (h_field holds its records)
+  int field_timed;          // ... and recorded ev_field
+  FpRecord* h_field;        // [B] the host side of field.b.hout
+  hipEvent_t ev_field[2];   // (created on first use)
+  uint64_t field_ns;        // k_field's time of the last collected batch (while profiling)
 };
 
 // Experiment and diagnostic knobs (stage cut-offs, grid / tile overrides, phase
@@ -378,6 +391,9 @@ void at_destroy(at_detector* d) {
   for (hipEvent_t e : d->ev_pv)
     if (e) (void)hipEventDestroy(e);
   if (d->d_pv) (void)hipFree(d->d_pv);
+  for (hipEvent_t e : d->ev_field)
+    if (e) (void)hipEventDestroy(e);
+  if (d->h_field) (void)hipHostFree(d->h_field);
   if (d->h_gp_out) (void)hipHostFree(d->h_gp_out);
   if (d->h_gp_info) (void)hipHostFree(d->h_gp_info);
   if (d->ev_done) (void)hipEventDestroy(d->ev_done);
@@ -730,7 +746,12 @@ static hipError_t record_sequence(at_detector* d, int nframes, int fmt, hipStrea
   hipError_t e;
   DevBufs b = d->d;
   b.kt_stage = kt ? kt->stage : -1;  // the timed kernel stamps its device-clock span
-  if ((e = launch_pipeline(b, d->g, d->prm, nframes, fmt, d->nblobwg, st, ev, d->st2, d->ev_fork, d->ev_join, kt)))
+  FieldLaunch fl = d->field;
+  // (events cannot be recorded between the segments of a split capture; stage profiling launches directly)
+  fl.ev[0] = ev ? d->ev_field[0] : nullptr;
+  fl.ev[1] = ev ? d->ev_field[1] : nullptr;
+  if ((e = launch_pipeline(b, d->g, d->prm, nframes, fmt, d->nblobwg, st, ev, d->st2, d->ev_fork, d->ev_join, kt,
+                           d->field_on ? &fl : nullptr)))
     return e;
   // results reach the host zero-copy: k_decode writes the detections into the
   // mapped host buffer and k_pose adds the poses and the control block; without
@@ -835,6 +856,8 @@ static int enqueue(at_detector* d, int nframes, int fmt) {
   d->last_gp = d->prm.gp_c && fmt == AT_FMT_BGR8;
   d->last_mj_color = 0;  // (at_enqueue_mjpg sets it after a colour-on batch)
   d->mj_ent_batch = 0;   // (... and this after a batch decoded by k_mjpg_entropy)
+  d->last_field = d->field_on && d->prm.tag_size > 0;
+  d->field_timed = d->last_field && d->profiling;
   d->pending = 1;
   return AT_OK;
 }
@@ -867,6 +890,13 @@ static int collect(at_detector* d, at_detection* out, int cap_per_frame, int* n_
       d->mj_stats[5] = (uint64_t)((double)ms * 1e6);
     }
     d->mj_timed = 0;
+  }
+  d->field_ns = 0;
+  if (d->field_timed) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, d->ev_field[0], d->ev_field[1]));
+    d->field_ns = (uint64_t)((double)ms * 1e6);
+    d->field_timed = 0;
   }
   if (d->mj_ent_timed) {
     float ms = 0;
@@ -2020,6 +2050,91 @@ int at_gp_enable(at_detector* d, int out_width, int out_height, int channels) {
   d->last_gp = 0;  // no tensor until a BGR8 batch has produced one
   drop_graphs(d);  // the captured sequences carry the old parameters
   return AT_OK;
+}
+
+// ---- field pose --------------------------------------------------------------
+// The layout lives in HBM (id table + tags, uploaded here, synchronously: no batch is
+// pending); k_field joins the launch sequence behind k_pose while a layout is set, so the
+// captured sequences are dropped whenever it changes.
+int at_set_field_layout(at_detector* d, const at_field_tag* tags, int n, int max_hamming) {
+  if (!d || max_hamming < 0 || !(d->prm.tag_size > 0) || d->pending) return AT_E_INVALID;
+  std::vector<int16_t> lut(kFpMaxIds);
+  std::vector<FpTag> lt;
+  const int rc = fp_build_layout(tags, n, lut.data(), &lt);
+  if (rc != AT_OK) return rc;
+  if (hipSetDevice(d->device) != hipSuccess) return AT_E_HIP;
+  if (n == 0) {
+    if (d->field_on) drop_graphs(d);
+    d->field_on = 0;
+    return AT_OK;
+  }
+  FieldBufs& fb = d->field.b;
+  if (!fb.out) {
+    const size_t B = (size_t)d->B;
+    void *plut = nullptr, *ptags = nullptr, *pout = nullptr;
+    FpRecord* hrec = nullptr;
+    void* hdev = nullptr;
+    bool ok = hipMalloc(&plut, kFpMaxIds * sizeof(int16_t)) == hipSuccess &&
+              hipMalloc(&ptags, kFpMaxIds * sizeof(FpTag)) == hipSuccess &&
+              hipMalloc(&pout, B * sizeof(FpRecord)) == hipSuccess &&
+              hipHostMalloc((void**)&hrec, B * sizeof(FpRecord), hipHostMallocMapped) == hipSuccess;
+    int err = ok ? AT_OK : AT_E_NOMEM;
+    if (ok && hipHostGetDevicePointer(&hdev, hrec, 0) != hipSuccess) err = AT_E_HIP;
+    if (err == AT_OK) {
+      for (int i = 0; i < 2 && err == AT_OK; i++)
+        if (!d->ev_field[i] && hipEventCreateWithFlags(&d->ev_field[i], kTimingEventFlags) != hipSuccess) err = AT_E_HIP;
+    }
+    if (err != AT_OK) {
+      if (plut) (void)hipFree(plut);
+      if (ptags) (void)hipFree(ptags);
+      if (pout) (void)hipFree(pout);
+      if (hrec) (void)hipHostFree(hrec);
+      return err;
+    }
+    d->allocs.push_back(plut);
+    d->allocs.push_back(ptags);
+    d->allocs.push_back(pout);
+    memset(hrec, 0, B * sizeof(FpRecord));
+    d->h_field = hrec;
+    fb.lay.lut = (const int16_t*)plut;
+    fb.lay.tags = (const FpTag*)ptags;
+    fb.out = (FpRecord*)pout;
+    fb.hout = (FpRecord*)hdev;
+  }
+  HIPCHK(hipMemcpy((void*)fb.lay.lut, lut.data(), kFpMaxIds * sizeof(int16_t), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy((void*)fb.lay.tags, lt.data(), lt.size() * sizeof(FpTag), hipMemcpyHostToDevice));
+  fb.lay.max_hamming = max_hamming;
+  d->field_on = 1;
+  drop_graphs(d);  // the captured sequences carry the old parameters
+  return AT_OK;
+}
+
+int at_field_poses(at_detector* d, at_field_pose* out, int cap) {
+  if (!d || cap < 0 || (cap > 0 && !out)) return AT_E_INVALID;
+  if (d->pending) return AT_E_INVALID;  // collect first
+  const int nf = d->last_nframes;
+  for (int f = 0; f < nf && f < cap; f++) {
+    if (d->last_field) fp_write(d->h_field[f], out + f);
+    else memset(out + f, 0, sizeof(*out));
+  }
+  return nf;
+}
+
+int at_field_stats(at_detector* d, uint64_t* out, int cap) {
+  if (!d || !out || cap < 1) return AT_E_INVALID;
+  if (d->pending) return AT_E_INVALID;
+  uint64_t v[5] = {0, 0, 0, 0, d->field_ns};
+  if (d->last_field)
+    for (int f = 0; f < d->last_nframes; f++) {
+      const FpRecord& r = d->h_field[f];
+      v[0] += r.n_tags > 0;
+      v[1] += (uint64_t)r.n_tags;
+      v[2] += (uint64_t)r.dropped;
+      v[3] += (uint64_t)r.rejected;
+    }
+  const int n = std::min(cap, 5);
+  for (int i = 0; i < n; i++) out[i] = v[i];
+  return n;
 }
 
 int at_gp_tensor(at_detector* d, int frame, const float** dev_ptr) {

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "at_detmath.h"
+#include "at_fieldpose.h"
 #include "at_preview.h"
 
 namespace at {
@@ -282,6 +283,18 @@ struct JpgBufs {
   uint32_t* row_len;    // [rows] ... after byte stuffing
   uint8_t* out;         // the entropy-coded data with RSTm and EOI, what follows the header
   uint32_t* total;      // bytes in `out` (mapped host memory)
+};
+
+// Field pose (at_set_field_layout): what k_field reads and writes, and the optional
+// timing events around its launch.  A launch sequence without a layout carries none.
+struct FieldBufs {
+  FpLayout lay;     // id table and tags in HBM, max_hamming
+  FpRecord* out;    // [B] one record per frame (HBM)
+  FpRecord* hout;   // [B] the same in mapped host memory (how k_pose mirrors its poses)
+};
+struct FieldLaunch {
+  FieldBufs b;
+  hipEvent_t ev[2];  // recorded around k_field when not null (stage profiling)
 };
 
 // Device buffers; every per-frame array is [max_batch][per-frame size].

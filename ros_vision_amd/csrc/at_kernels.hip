@@ -5953,6 +5953,59 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AT_POSE_WAVE
 }
 
 // ---------------------------------------------------------------------------
+// Field pose (at_set_field_layout): one camera pose per frame from all its layout
+// tags, after k_pose (it starts from the tags' own poses).  One wave per frame, one
+// lane per corner slot (4 x 16); the algorithm is fp_solve_frame of at_fieldpose.h,
+// which at_field_pose_host runs with one thread holding the 64 slots.  The sums cross
+// the wave as the xor butterfly 32, 16, .. 1 (the order the header fixes); every lane
+// solves the 6 x 6 system redundantly: no LDS, no barrier.  Lane 0 stores the record to
+// HBM and to the mapped host buffer.
+// ---------------------------------------------------------------------------
+struct FpWave {
+  static constexpr int NS = 1;
+  int lane;
+  __device__ int slot(int) const { return lane; }
+  __device__ bool leader() const { return lane == 0; }
+  __device__ double sum(const double* v) const {
+    double a = v[0];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) a = a + __shfl_xor(a, off);
+    return a;
+  }
+  __device__ bool any(const bool* f) const { return __any(f[0]) != 0; }
+  __device__ uint64_t min(const uint64_t* v) const {
+    uint64_t a = v[0];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)a, off);
+      a = o < a ? o : a;
+    }
+    return a;
+  }
+  __device__ uint32_t from_slot(const uint32_t* v, int slot) const { return (uint32_t)__shfl((int)v[0], slot); }
+};
+struct FpDevSrc {
+  const DevDetection* d;  // the frame's candidate slots
+  int count;
+  __device__ int n() const { return count; }
+  __device__ int32_t id(int c) const { return d[c].id; }
+  __device__ int32_t hamming(int c) const { return d[c].hamming; }
+  __device__ float margin(int c) const { return d[c].decision_margin; }
+  __device__ const double* p(int c) const { return &d[c].p[0][0]; }
+  __device__ const double* pose_R(int c) const { return d[c].pose_R; }
+  __device__ const double* pose_t(int c) const { return d[c].pose_t; }
+};
+__global__ __launch_bounds__(64) void k_field(DevBufs b, FieldBufs fb, Params prm, int nframes) {
+  const int f = (int)blockIdx.x;
+  if (f >= nframes) return;
+  const uint32_t nd = b.ndets[f];
+  const FpDevSrc src = {b.dets + (size_t)f * kMaxDets, (int)(nd < (uint32_t)kMaxDets ? nd : (uint32_t)kMaxDets)};
+  const FpCam cam = {prm.fx, prm.fy, prm.cx, prm.cy};
+  const FpWave w = {(int)threadIdx.x};
+  fp_solve_frame(w, src, fb.lay, cam, prm.tag_size, fb.out + f, fb.hout + f);
+}
+
+// ---------------------------------------------------------------------------
 // Shared game-piece preprocessing: preprocess_image of
 // src/game_piece_detection/src/game_piece_detection_node.cu:347-379 --
 // cv::resize (INTER_LINEAR, 8UC3), BGR->RGB (3 channels) or BGR->GRAY (1),
@@ -7240,7 +7293,7 @@ hipError_t prepare_kernels(const Geom& g) {
 
 hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, int B, int fmt, int nblobwg,
                            hipStream_t st, hipEvent_t* ev, hipStream_t st2, hipEvent_t fork, hipEvent_t join,
-                           const KernelTimer* kt) {
+                           const KernelTimer* kt, const FieldLaunch* field) {
   int e = 0;
   auto on = [&](int stage) { return AT_PIPE_STOP(prm) <= 0 || stage < AT_PIPE_STOP(prm); };
   auto mark = [&]() {
@@ -7430,6 +7483,13 @@ hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, i
   }
   tk(11, st, 1);
   mark();
+  // field pose (at_set_field_layout): after the poses it starts from; no stage of its own
+  // (its time: at_field_stats)
+  if (field && prm.tag_size > 0 && on(11)) {
+    if (field->ev[0]) (void)hipEventRecord(field->ev[0], st);
+    hipLaunchKernelGGL(k_field, dim3(B), dim3(64), 0, st, b, field->b, prm, B);
+    if (field->ev[1]) (void)hipEventRecord(field->ev[1], st);
+  }
   if (split_err != hipSuccess) return split_err;
   return hipGetLastError();
 }

@@ -44,7 +44,9 @@ EXPORTS = [
     "at_mjpg_set_device_entropy", "at_mjpg_set_subseq", "at_mjpg_entropy_host", "at_mjpg_dense_host",
     "at_preview_size", "at_preview_bgr", "at_preview_jpeg", "at_preview_jpeg_device", "at_preview_host",
     "at_preview_jpeg_host", "at_preview_stats",
+    "at_set_field_layout", "at_field_poses", "at_field_pose_host", "at_robot_in_field", "at_field_stats",
 ]
+AT_FIELD_MAX_TAGS = 16
 AT_GP_MAX_CANDIDATES = 4096
 # at_gp_box as a numpy record (the bit-exact view of what the library wrote)
 GP_BOX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("conf", "<f4"), ("cls", "<i4")])
@@ -83,6 +85,15 @@ class AtTagDetection(C.Structure):
                 ("distance", C.c_double), ("err", C.c_double)]
 
 
+class AtFieldTag(C.Structure):
+    _fields_ = [("id", C.c_int32), ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+class AtFieldPose(C.Structure):
+    _fields_ = [("n_tags", C.c_int32), ("ids", C.c_int32 * AT_FIELD_MAX_TAGS), ("R", C.c_double * 9),
+                ("t", C.c_double * 3), ("rms_px", C.c_double), ("steps_taken", C.c_int32)]
+
+
 class AtQuadRecord(C.Structure):
     _fields_ = [
         ("blob_index", C.c_uint32), ("valid", C.c_uint32), ("accepted", C.c_uint32),
@@ -119,6 +130,18 @@ class TagDetection:
     robot: np.ndarray
     distance: float
     err: float
+
+
+@dataclass
+class FieldPose:
+    """at_field_pose: the camera pose of one frame from all its layout tags, x_cam = R x_field + t
+    (n_tags == 0: no layout tag in the frame, the rest zero)."""
+    n_tags: int
+    ids: list
+    R: np.ndarray
+    t: np.ndarray
+    rms_px: float
+    steps_taken: int
 
 
 @dataclass
@@ -270,6 +293,14 @@ def load_library(path: str = LIB_PATH):
         L.at_preview_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + recs + [C.c_void_p, C.c_size_t]
         L.at_preview_jpeg_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + recs + jpeg_tail
         L.at_preview_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+    if hasattr(L, "at_field_poses"):  # (A/B builds of older sources lack the field pose)
+        dp = C.POINTER(C.c_double)
+        L.at_set_field_layout.argtypes = [C.c_void_p, C.POINTER(AtFieldTag), C.c_int, C.c_int]
+        L.at_field_poses.argtypes = [C.c_void_p, C.POINTER(AtFieldPose), C.c_int]
+        L.at_field_pose_host.argtypes = [C.POINTER(AtDetection), C.POINTER(AtPose), C.c_int, C.POINTER(AtFieldTag),
+                                         C.c_int, C.c_int, C.POINTER(AtCamera), C.c_double, C.POINTER(AtFieldPose)]
+        L.at_robot_in_field.argtypes = [C.POINTER(AtFieldPose), dp, dp, dp, dp]
+        L.at_field_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
     _LIB = L
     return L
 
@@ -610,6 +641,86 @@ def tag_detections(poses, extrinsic_rotation=None, extrinsic_offset=None):
                          distance=o.distance, err=o.err) for o in out[:n]]
 
 
+class FieldPoseError(RuntimeError):
+    """A field-pose call the library refused; `code` is the AT_E_* value (AT_E_INVALID: a bad
+    layout, tag_size 0, a batch not yet collected, a record without tags)."""
+
+    def __init__(self, what, code):
+        super().__init__("%s failed: %s (%d)" % (what, load_library().at_strerror(code).decode(), code))
+        self.code = code
+
+
+def _field_tags(tags):
+    """A layout -- (id, R, t) triples -- as at_field_tag records."""
+    tags = list(tags or ())
+    arr = (AtFieldTag * max(1, len(tags)))()
+    for i, (tid, R, t) in enumerate(tags):
+        arr[i].id = int(tid)
+        arr[i].R[:] = [float(x) for x in np.asarray(R, np.float64).reshape(9)]
+        arr[i].t[:] = [float(x) for x in np.asarray(t, np.float64).reshape(3)]
+    return arr, len(tags)
+
+
+def _field_pose(o):
+    return FieldPose(n_tags=o.n_tags, ids=[int(x) for x in o.ids[:o.n_tags]], R=np.array(list(o.R)).reshape(3, 3),
+                     t=np.array(list(o.t)), rms_px=o.rms_px, steps_taken=o.steps_taken)
+
+
+def _field_pose_record(fp):
+    o = AtFieldPose()
+    o.n_tags = int(fp.n_tags)
+    for i, tid in enumerate(fp.ids):
+        o.ids[i] = int(tid)
+    o.R[:] = [float(x) for x in np.asarray(fp.R, np.float64).reshape(9)]
+    o.t[:] = [float(x) for x in np.asarray(fp.t, np.float64).reshape(3)]
+    o.rms_px, o.steps_taken = float(fp.rms_px), int(fp.steps_taken)
+    return o
+
+
+def field_pose_host(detections, poses, tags, max_hamming=0, camera_matrix=None, tag_size=TAG_SIZE):
+    """at_field_pose_host: the field pose of one frame on the CPU, from its detections() and
+    poses() (same order) and a layout of (id, R, t) triples -- the reference the GPU path
+    (GpuDetector.field_poses) is held to.  Raises FieldPoseError for a layout or tag_size the
+    library refuses."""
+    L = load_library()
+    cam = camera_matrix or TEST_CAMERA
+    if len(detections) != len(poses):
+        raise ValueError("one pose per detection")
+    (darr, n), tarr_n = _detection_records(detections), _field_tags(tags)
+    parr = (AtPose * max(1, n))()
+    for i, p in enumerate(poses):
+        parr[i].id = int(p.id)
+        parr[i].R[:] = [float(x) for x in np.asarray(p.R, np.float64).reshape(9)]
+        parr[i].t[:] = [float(x) for x in np.asarray(p.t, np.float64).reshape(3)]
+        parr[i].err = float(p.err)
+    c = AtCamera(fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy)
+    out = AtFieldPose()
+    rc = L.at_field_pose_host(darr, parr, n, tarr_n[0], tarr_n[1], int(max_hamming), C.byref(c), float(tag_size),
+                              C.byref(out))
+    if rc < 0:
+        raise FieldPoseError("at_field_pose_host", rc)
+    return _field_pose(out)
+
+
+def robot_in_field(field_pose, extrinsic_rotation=None, extrinsic_offset=None):
+    """at_robot_in_field: (R, t) of the robot in the field, field_T_cam (robot_T_cam)^-1, from a
+    FieldPose and the camera -> robot extrinsics tag_detections takes.  Host only."""
+    Rp = tp = None
+    dp = C.POINTER(C.c_double)
+    if extrinsic_rotation is not None:
+        Rv = np.ascontiguousarray(extrinsic_rotation, np.float64).reshape(9)
+        Rp = Rv.ctypes.data_as(dp)
+    if extrinsic_offset is not None:
+        tv = np.ascontiguousarray(extrinsic_offset, np.float64).reshape(3)
+        tp = tv.ctypes.data_as(dp)
+    R, t = np.empty(9), np.empty(3)
+    rec = _field_pose_record(field_pose)
+    rc = load_library().at_robot_in_field(C.byref(rec), Rp, tp, R.ctypes.data_as(dp), t.ctypes.data_as(dp))
+    if rc < 0:
+        raise FieldPoseError("at_robot_in_field", rc)
+    return R.reshape(3, 3), t
+
+
 def _check(rc, what):
     if rc < 0:
         raise RuntimeError("%s failed: %s (%d)" % (what, load_library().at_strerror(rc).decode(), rc))
@@ -851,6 +962,32 @@ class GpuDetector:
         n = _check(load_library().at_poses(self._h, frame, buf, cap), "at_poses")
         return [Pose(id=b.id, R=np.array(list(b.R)).reshape(3, 3), t=np.array(list(b.t)), err=b.err)
                 for b in buf[:min(n, cap)]]
+
+    # ---- field pose (k_field) ------------------------------------------------
+    def set_field_layout(self, tags, max_hamming=0):
+        """at_set_field_layout: where each tag stands on the field -- (id, R, t) triples,
+        x_field = R x_tag + t -- from the next batch on; empty or None clears it.  Raises
+        FieldPoseError (AT_E_INVALID) for a bad layout, tag_size 0 or a batch not yet collected."""
+        arr, n = _field_tags(tags)
+        rc = load_library().at_set_field_layout(self._h, arr, n, int(max_hamming))
+        if rc < 0:
+            raise FieldPoseError("at_set_field_layout", rc)
+
+    def field_poses(self):
+        """at_field_poses: one FieldPose per frame of the last collected batch."""
+        buf = (AtFieldPose * self.max_batch)()
+        rc = load_library().at_field_poses(self._h, buf, self.max_batch)
+        if rc < 0:
+            raise FieldPoseError("at_field_poses", rc)
+        return [_field_pose(b) for b in buf[:rc]]
+
+    FIELD_STATS = ("frames_solved", "tags_used", "dropped_by_cap", "rejected_steps", "kernel_ns")
+
+    def field_stats(self):
+        """at_field_stats of the last collected batch."""
+        buf = (C.c_uint64 * len(self.FIELD_STATS))()
+        n = _check(load_library().at_field_stats(self._h, buf, len(buf)), "at_field_stats")
+        return dict(zip(self.FIELD_STATS, [int(x) for x in buf[:n]]))
 
     def collect(self, counts_only=False):
         """at_collect: wait for the batch, run the host tail.  The detections land in

@@ -31,7 +31,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .detector import (AT_FMT_BGR8, AT_FMT_GRAY8, AT_FMT_YUYV, TAG_SIZE, CameraMatrix, DistCoeffs, GpuDetector,
-                       tag_detections)
+                       robot_in_field, tag_detections)
 
 PARAMETER_DEFAULTS = {
     "topic_name": "camera/image_raw",
@@ -85,6 +85,19 @@ def load_extrinsics(system_config_path, camera_serial):
         return R, t, location
     return (np.array(extr["rotation"], np.float64).reshape(3, 3), np.array(extr["offset"], np.float64).reshape(3),
             location)
+
+
+def load_field_layout(layout):
+    """A field layout -- where each tag stands on the field, x_field = R x_tag + t, the tag frame
+    being at_pose's -- as a list of (id, R 3x3, t 3): from such a list, or from the path of a JSON
+    file {"tags": [{"id": 4, "R": [r00 .. r22], "t": [tx, ty, tz]}, ...]} (this project's own
+    format; WPILib's field layout files and their tag-frame convention are not read)."""
+    if isinstance(layout, (str, os.PathLike)):
+        with open(layout) as f:
+            data = json.load(f)
+        layout = [(g["id"], g["R"], g["t"]) for g in data["tags"]]
+    return [(int(tid), np.array(R, np.float64).reshape(3, 3), np.array(t, np.float64).reshape(3))
+            for tid, R, t in layout]
 
 
 def draw_detection_outlines(bgr, dets):
@@ -256,6 +269,8 @@ class FrameResult:
     image: np.ndarray = None
     image_jpeg: bytes = None                                          # image_jpeg set: the image as JPEG instead
     preview_jpeg: bytes = None                                        # preview_scale > 0: the scaled annotated JPEG
+    field_pose: object = None          # field_layout set: the frame's FieldPose (camera in the field; n_tags 0: none)
+    robot_in_field: tuple = None       # ... and (R, t) of the robot in the field, when the frame has a field pose
 
 
 class ApriltagsDetectorNode:
@@ -263,7 +278,7 @@ class ApriltagsDetectorNode:
 
     def __init__(self, width, height, parameters=None, calibration_dir=None, system_config_path=None,
                  publishers=None, device=0, mjpg_color=False, image_jpeg=None, mjpg_device_entropy=False,
-                 preview_scale=0, preview_quality=50, preview_max_bytes=0):
+                 preview_scale=0, preview_quality=50, preview_max_bytes=0, field_layout=None, field_max_hamming=0):
         self.params = dict(PARAMETER_DEFAULTS)
         self.params.update(parameters or {})
         serial = self.params["camera_serial"]
@@ -301,6 +316,13 @@ class ApriltagsDetectorNode:
         self.preview_scale, self.preview_quality, self.preview_max_bytes = _preview_options(
             preview_scale, preview_quality, preview_max_bytes)
         self.preview_topic = self.image_topic + "/preview/compressed"
+        # field_layout = [(id, R, t), ...] or the path of a layout JSON (load_field_layout): the GPU
+        # also solves every frame's camera pose from all its layout tags (k_field), and the robot's
+        # pose in the field -- (R, t), x_field = R x_robot + t -- goes out on <publish_pose_to_topic>/field
+        self.field_layout = load_field_layout(field_layout) if field_layout is not None else None
+        self.field_pose_topic = self.pose_topic + "/field"
+        if self.field_layout:
+            self.detector.set_field_layout(self.field_layout, field_max_hamming)
         self.csv = None
         if self.params["measurement_mode"]:
             path = self.params["timing_csv_path"] or time.strftime("apriltags_timing_%Y%m%d_%H%M%S.csv")
@@ -347,6 +369,10 @@ class ApriltagsDetectorNode:
             res.proto_tags.append({"collect_time": stamp_s, "tag_id": tag.id, "x": rx, "y": ry, "z": rz})
             res.tag_detection_camera_array.append((tag.id, *(float(v) for v in tag.camera)))
             res.tag_detection_array.append((tag.id, rx, ry, rz))
+        if self.field_layout:
+            res.field_pose = self.detector.field_poses()[0]
+            if res.field_pose.n_tags:
+                res.robot_in_field = robot_in_field(res.field_pose, self.extrinsic_rotation, self.extrinsic_offset)
         if self.preview_scale:
             # (first: at_annotate_staged / at_annotate_jpeg below draw on the staged frame itself)
             res.preview_jpeg = _preview_or_none(lambda: self.detector.preview_jpeg(
@@ -365,6 +391,8 @@ class ApriltagsDetectorNode:
         self._publish(self.pose_topic, res.tag_detection_array)
         pp1 = time.perf_counter()
         self._publish(self.camera_pose_topic, res.tag_detection_camera_array)
+        if res.robot_in_field is not None:
+            self._publish(self.field_pose_topic, res.robot_in_field)
         pc1 = time.perf_counter()
         if res.image is not None:
             self._publish(self.image_topic, res.image)
