@@ -602,6 +602,73 @@ int at_field_pose_host(const at_detection *dets, const at_pose *poses, int n, co
 int at_robot_in_field(const at_field_pose *fp, const double *extr_R, const double *extr_t, double *R_out, double *t_out);
 int at_field_stats(at_detector *d, uint64_t *out, int cap);
 
+/* Rig pose: one robot pose per instant from the layout tags of every camera, with its covariance.
+ *
+ * A rig is 1..AT_RIG_MAX_CAMS detectors of one process on one device, each with its own
+ * at_camera and its extrinsics x_robot = R x_cam + t (at_tag_detections' convention); frame f of
+ * every member's last batch is instant f.  The unknown is the robot in the field,
+ * x_field = R x_robot + t.  One kernel (k_rig, one workgroup per instant, one wave per camera)
+ * on the rig's own stream; it is part of no member's launch sequence, reads the members'
+ * candidates and writes nothing of theirs.
+ *
+ * Per instant:
+ *   select  per camera as the field pose does (at most AT_FIELD_MAX_TAGS tags each);
+ *   points  a corner X of the field projects as Q = R^T (X - t), P = E_R^T (Q - E_t),
+ *           u = fx Px / Pz + cx, v = fy Py / Pz + cy against at_detection.p; Pz <= 0: infinite cost;
+ *   start   each selected tag's own pose as a robot pose,
+ *           field_T_tag (cam_T_tag)^-1 (robot_T_cam)^-1; the one with the least summed squared
+ *           reprojection error over all corners of all cameras (ties: the lower camera, then
+ *           the lower id), its rotation made orthonormal;
+ *   refine  12 Levenberg-Marquardt iterations as the field pose's, parameters (w, dt) with
+ *           R' = R dR(w) (w in the robot frame, dR from q = (1, w / 2) normalised) and
+ *           t' = t + dt (field frame);
+ *   cov     sigma^2 (J^T J)^-1 at the final pose, sigma^2 = cost / (8 n_tags - 6), row-major
+ *           6 x 6 in the order (w_x, w_y, w_z, t_x, t_y, t_z): cov[21], cov[28], cov[35] are the
+ *           field-frame position variances, cov[14] the variance of the turn about the robot's
+ *           z.  cov_valid = 0 (and zeros) when J^T J has no Cholesky factor.
+ * An instant without a layout tag in any camera has n_tags = 0 and the rest zero.
+ *
+ * at_rig_create: AT_E_INVALID for n_cams outside 1..AT_RIG_MAX_CAMS, a NULL member, a member
+ * twice, members on different devices, at_config.tag_size 0 or differing between members, a
+ * layout at_set_field_layout would refuse (n_tags = 0 included), max_hamming < 0.  The members
+ * need no field layout of their own and must outlive the rig.
+ * at_rig_solve: the members' last batches (pending or collected; it waits for them on its own
+ * stream and does not collect them) must have one frame count, else AT_E_INVALID, as when a
+ * member has run none.  Returns the number of instants, writes at most cap records.
+ * at_rig_stats, the last solve: [0] instants solved, [1] tags used, [2] candidates dropped by the
+ * per-camera cap, [3] rejected LM steps, [4] k_rig's time in nanoseconds (HIP events; while
+ * at_set_profiling is on for a member, 0 otherwise).
+ * at_rig_pose_host: the same solve on the CPU for one instant (the CPU reference: the kernel's
+ * arithmetic in the kernel's order, bit-equal records). */
+#define AT_RIG_MAX_CAMS 8
+typedef struct { double R[9]; double t[3]; } at_rig_extrinsics;     /* x_robot = R x_cam + t */
+typedef struct {
+  int32_t n_tags;                                      /* total over the cameras; 0: rest zeroed */
+  int32_t n_cams_used;                                 /* cameras with at least one tag */
+  int32_t tags_per_cam[AT_RIG_MAX_CAMS];
+  int32_t ids[AT_RIG_MAX_CAMS][AT_FIELD_MAX_TAGS];     /* per camera, ascending */
+  double R[9]; double t[3];                            /* x_field = R x_robot + t, row-major */
+  double cov[36];
+  double rms_px;                                       /* reprojection RMS over the 4*n_tags corners */
+  int32_t cov_valid;
+  int32_t steps_taken;                                 /* accepted LM steps */
+  int32_t rejected;                                    /* LM steps not taken */
+  int32_t dropped;                                     /* eligible candidates beyond a camera's 16 lowest ids */
+} at_rig_pose;
+typedef struct {
+  const at_detection *dets; const at_pose *poses; int32_t n;   /* one frame's at_detections / at_poses */
+  const at_camera *cam;
+  at_rig_extrinsics extr;
+} at_rig_host_cam;
+typedef struct at_rig at_rig;
+int at_rig_create(at_detector *const *dets, const at_rig_extrinsics *extr, int n_cams,
+                  const at_field_tag *tags, int n_tags, int max_hamming, at_rig **out);
+int at_rig_solve(at_rig *r, at_rig_pose *out, int cap);
+int at_rig_stats(at_rig *r, uint64_t *out, int cap);
+void at_rig_destroy(at_rig *r);
+int at_rig_pose_host(const at_rig_host_cam *cams, int n_cams, const at_field_tag *tags, int n_tags,
+                     int max_hamming, double tag_size, at_rig_pose *out);
+
 /* Page-locked host memory (hipHostMalloc) for buffers the detector copies into on
  * its stream by DMA, e.g. at_annotate_staged's bgr_out: a pageable destination
  * goes through the runtime's staging buffers instead.  (No counterpart in the

@@ -50,6 +50,11 @@ hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, i
 // (at_fieldpose.cpp)
 int fp_build_layout(const at_field_tag* tags, int n, int16_t* lut, std::vector<FpTag>* out);
 void fp_write(const FpRecord& r, at_field_pose* o);
+// (at_rigpose.cpp)
+bool rig_extrinsics_ok(const at_rig_extrinsics& e);
+void rig_write(const RigRecord& r, at_rig_pose* o);
+// (at_kernels.hip)
+hipError_t launch_rig(const RigBufs& rb, int ninstants, hipStream_t st);
 
 struct CodeEntry {
   int id;
@@ -2132,6 +2137,147 @@ int at_field_stats(at_detector* d, uint64_t* out, int cap) {
       v[2] += (uint64_t)r.dropped;
       v[3] += (uint64_t)r.rejected;
     }
+  const int n = std::min(cap, 5);
+  for (int i = 0; i < n; i++) out[i] = v[i];
+  return n;
+}
+
+// ---- rig pose ------------------------------------------------------------------
+// The rig owns its stream, its copy of the layout in HBM and one record per instant in HBM and
+// in mapped host memory; of its members it holds pointers only (their candidates, counts and
+// completion events), and k_rig reads them.
+struct at_rig {
+  int n_cams;
+  int device;
+  int B;                     // most instants: the smallest max_batch of the members
+  at_detector* det[kRigMaxCams];
+  hipStream_t st;
+  hipEvent_t ev[2];          // around k_rig while a member profiles
+  RigBufs b;
+  void *d_lut, *d_tags, *d_out;
+  RigRecord* h_out;          // [B] the host side of b.hout
+  int last_n;                // instants of the last solve
+  uint64_t ns;               // k_rig's time of the last solve (while profiling)
+};
+
+void at_rig_destroy(at_rig* r) {
+  if (!r) return;
+  (void)hipSetDevice(r->device);
+  if (r->st) (void)hipStreamSynchronize(r->st);
+  if (r->d_lut) (void)hipFree(r->d_lut);
+  if (r->d_tags) (void)hipFree(r->d_tags);
+  if (r->d_out) (void)hipFree(r->d_out);
+  if (r->h_out) (void)hipHostFree(r->h_out);
+  for (hipEvent_t e : r->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (r->st) (void)hipStreamDestroy(r->st);
+  delete r;
+}
+
+int at_rig_create(at_detector* const* dets, const at_rig_extrinsics* extr, int n_cams, const at_field_tag* tags,
+                  int n_tags, int max_hamming, at_rig** out) {
+  if (!out || !dets || !extr || n_cams < 1 || n_cams > kRigMaxCams || max_hamming < 0 || n_tags < 1)
+    return AT_E_INVALID;
+  int B = 0;
+  for (int i = 0; i < n_cams; i++) {
+    const at_detector* d = dets[i];
+    if (!d || !(d->prm.tag_size > 0) || d->device != dets[0]->device || d->prm.tag_size != dets[0]->prm.tag_size)
+      return AT_E_INVALID;
+    for (int k = 0; k < i; k++)
+      if (dets[k] == d) return AT_E_INVALID;
+    if (!rig_extrinsics_ok(extr[i])) return AT_E_INVALID;
+    B = i ? std::min(B, d->B) : d->B;
+  }
+  std::vector<int16_t> lut(kFpMaxIds);
+  std::vector<FpTag> lt;
+  const int rc = fp_build_layout(tags, n_tags, lut.data(), &lt);
+  if (rc != AT_OK) return rc;
+  if (hipSetDevice(dets[0]->device) != hipSuccess) return AT_E_HIP;
+  at_rig* r = new at_rig();
+  r->n_cams = n_cams;
+  r->device = dets[0]->device;
+  r->B = B;
+  void* hdev = nullptr;
+  int err = AT_OK;
+  if (hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking) != hipSuccess) err = AT_E_HIP;
+  for (int i = 0; i < 2 && err == AT_OK; i++)
+    if (hipEventCreateWithFlags(&r->ev[i], kTimingEventFlags) != hipSuccess) err = AT_E_HIP;
+  if (err == AT_OK && !(hipMalloc(&r->d_lut, kFpMaxIds * sizeof(int16_t)) == hipSuccess &&
+                        hipMalloc(&r->d_tags, lt.size() * sizeof(FpTag)) == hipSuccess &&
+                        hipMalloc(&r->d_out, (size_t)B * sizeof(RigRecord)) == hipSuccess &&
+                        hipHostMalloc((void**)&r->h_out, (size_t)B * sizeof(RigRecord), hipHostMallocMapped) ==
+                            hipSuccess))
+    err = AT_E_NOMEM;
+  if (err == AT_OK && hipHostGetDevicePointer(&hdev, r->h_out, 0) != hipSuccess) err = AT_E_HIP;
+  if (err == AT_OK && !(hipMemcpy(r->d_lut, lut.data(), kFpMaxIds * sizeof(int16_t), hipMemcpyHostToDevice) ==
+                            hipSuccess &&
+                        hipMemcpy(r->d_tags, lt.data(), lt.size() * sizeof(FpTag), hipMemcpyHostToDevice) ==
+                            hipSuccess))
+    err = AT_E_HIP;
+  if (err != AT_OK) {
+    at_rig_destroy(r);
+    return err;
+  }
+  memset(r->h_out, 0, (size_t)B * sizeof(RigRecord));
+  RigBufs& b = r->b;
+  for (int i = 0; i < n_cams; i++) {
+    at_detector* d = dets[i];
+    r->det[i] = d;
+    RigCamView& v = b.view[i];
+    v.dets = d->d.dets;
+    v.ndets = d->d.ndets;
+    v.cam = {d->prm.fx, d->prm.fy, d->prm.cx, d->prm.cy, {}, {}};
+    memcpy(v.cam.ER, extr[i].R, sizeof(v.cam.ER));
+    memcpy(v.cam.Et, extr[i].t, sizeof(v.cam.Et));
+  }
+  b.lay.lut = (const int16_t*)r->d_lut;
+  b.lay.tags = (const FpTag*)r->d_tags;
+  b.lay.max_hamming = max_hamming;
+  b.out = (RigRecord*)r->d_out;
+  b.hout = (RigRecord*)hdev;
+  b.tag_size = dets[0]->prm.tag_size;
+  b.n_cams = n_cams;
+  *out = r;
+  return AT_OK;
+}
+
+int at_rig_solve(at_rig* r, at_rig_pose* out, int cap) {
+  if (!r || cap < 0 || (cap > 0 && !out)) return AT_E_INVALID;
+  const int n = r->det[0]->last_nframes;
+  if (n < 1 || n > r->B) return AT_E_INVALID;
+  bool timed = false;
+  for (int i = 0; i < r->n_cams; i++) {
+    if (r->det[i]->last_nframes != n) return AT_E_INVALID;
+    timed = timed || r->det[i]->profiling;
+  }
+  if (hipSetDevice(r->device) != hipSuccess) return AT_E_HIP;
+  // behind every member's batch (an event of a batch already collected is complete)
+  for (int i = 0; i < r->n_cams; i++) HIPCHK(hipStreamWaitEvent(r->st, r->det[i]->ev_done, 0));
+  if (timed) HIPCHK(hipEventRecord(r->ev[0], r->st));
+  HIPCHK(launch_rig(r->b, n, r->st));
+  if (timed) HIPCHK(hipEventRecord(r->ev[1], r->st));
+  HIPCHK(hipStreamSynchronize(r->st));
+  r->ns = 0;
+  if (timed) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, r->ev[0], r->ev[1]));
+    r->ns = (uint64_t)((double)ms * 1e6);
+  }
+  r->last_n = n;
+  for (int f = 0; f < n && f < cap; f++) rig_write(r->h_out[f], out + f);
+  return n;
+}
+
+int at_rig_stats(at_rig* r, uint64_t* out, int cap) {
+  if (!r || !out || cap < 1) return AT_E_INVALID;
+  uint64_t v[5] = {0, 0, 0, 0, r->ns};
+  for (int f = 0; f < r->last_n; f++) {
+    const RigRecord& q = r->h_out[f];
+    v[0] += q.n_tags > 0;
+    v[1] += (uint64_t)q.n_tags;
+    v[2] += (uint64_t)q.dropped;
+    v[3] += (uint64_t)q.rejected;
+  }
   const int n = std::min(cap, 5);
   for (int i = 0; i < n; i++) out[i] = v[i];
   return n;

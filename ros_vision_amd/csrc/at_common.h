@@ -6,6 +6,7 @@
 
 #include "at_detmath.h"
 #include "at_fieldpose.h"
+#include "at_rigpose.h"
 #include "at_preview.h"
 
 namespace at {
@@ -295,6 +296,23 @@ struct FieldBufs {
 struct FieldLaunch {
   FieldBufs b;
   hipEvent_t ev[2];  // recorded around k_field when not null (stage profiling)
+};
+
+// Rig pose (at_rig_create): what k_rig reads of each member camera -- its candidates and
+// their counts (the member's DevBufs::dets / ndets), its intrinsics and extrinsics -- passed
+// by value, and where it writes.  Nothing here belongs to a detector but what is const.
+struct RigCamView {
+  const DevDetection* dets;  // [B][kMaxDets]
+  const uint32_t* ndets;     // [B]
+  RigCam cam;
+};
+struct RigBufs {
+  RigCamView view[kRigMaxCams];
+  FpLayout lay;      // id table and tags in HBM, max_hamming
+  RigRecord* out;    // [B] one record per instant (HBM)
+  RigRecord* hout;   // [B] the same in mapped host memory
+  double tag_size;
+  int n_cams;
 };
 
 // Device buffers; every per-frame array is [max_batch][per-frame size].

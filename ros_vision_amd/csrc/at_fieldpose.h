@@ -264,16 +264,14 @@ AT_FP_HD double fp_cost(const W& w, const FpSlot* slots, const FpCam& cam, const
   return w.sum(e);
 }
 
-// Src: the frame's candidates -- n(), id(c), hamming(c), margin(c), p(c) (8 doubles:
-// the four corners' pixels), pose_R(c) (9), pose_t(c) (3).
-// Every thread of the wave ends with the same record; the leader stores it to out (and
-// out2 when given).
+// ---- select: the best candidate of each of the 16 lowest layout ids ----
+// Slot 4j + c ends with the candidate (my_cand) and id (my_id) of the j-th selected tag; *m_out
+// tags were selected, *dropped_out eligible candidates had an id beyond them.  (k_rig and its
+// twin run this once per camera: at_rigpose.h.)
 template <class W, class Src>
-AT_FP_HD void fp_solve_frame(const W& w, const Src& src, const FpLayout& lay, const FpCam& cam, double tag_size,
-                             FpRecord* out, FpRecord* out2) {
+AT_FP_HD void fp_select(const W& w, const Src& src, const FpLayout& lay, uint32_t* my_cand, uint32_t* my_id,
+                        int* m_out, int* dropped_out) {
   const int n = src.n() < kFpMaxCand ? src.n() : kFpMaxCand;
-  // ---- select: the best candidate of each of the 16 lowest layout ids ----
-  uint32_t my_cand[W::NS], my_id[W::NS];
 #pragma unroll
   for (int s = 0; s < W::NS; s++) my_cand[s] = my_id[s] = 0;
   // (a slot's first candidate, the only one in a frame of up to 64, is read once; the rounds
@@ -315,10 +313,15 @@ AT_FP_HD void fp_solve_frame(const W& w, const Src& src, const FpLayout& lay, co
     m++;
     floor_key = ((best >> 52) + 1) << 52;
   }
+  *m_out = m;
+  *dropped_out = dropped;
+}
 
-  // ---- points ----
+// ---- points: each slot's corner in the field frame and its pixel ----
+template <class W, class Src>
+AT_FP_HD void fp_points(const W& w, const Src& src, const FpLayout& lay, double tag_size, int m,
+                        const uint32_t* my_cand, const uint32_t* my_id, FpSlot* slots) {
   const double hs = tag_size / 2.0;
-  FpSlot slots[W::NS];
 #pragma unroll
   for (int s = 0; s < W::NS; s++) {
     const int sl = w.slot(s), j = sl >> 2, c = sl & 3;
@@ -334,6 +337,20 @@ AT_FP_HD void fp_solve_frame(const W& w, const Src& src, const FpLayout& lay, co
       q.v = p[c * 2 + 1];
     }
   }
+}
+
+// Src: the frame's candidates -- n(), id(c), hamming(c), margin(c), p(c) (8 doubles:
+// the four corners' pixels), pose_R(c) (9), pose_t(c) (3).
+// Every thread of the wave ends with the same record; the leader stores it to out (and
+// out2 when given).
+template <class W, class Src>
+AT_FP_HD void fp_solve_frame(const W& w, const Src& src, const FpLayout& lay, const FpCam& cam, double tag_size,
+                             FpRecord* out, FpRecord* out2) {
+  uint32_t my_cand[W::NS], my_id[W::NS];
+  int m, dropped;
+  fp_select(w, src, lay, my_cand, my_id, &m, &dropped);
+  FpSlot slots[W::NS];
+  fp_points(w, src, lay, tag_size, m, my_cand, my_id, slots);
 
   // ---- start: the single-tag pose with the least total error ----
   double R[9], t[3];

@@ -6006,6 +6006,107 @@ __global__ __launch_bounds__(64) void k_field(DevBufs b, FieldBufs fb, Params pr
 }
 
 // ---------------------------------------------------------------------------
+// Rig pose (at_rig_create): one robot pose per instant from the layout tags of every
+// camera of a rig.  One workgroup per instant, one wave per camera (blockDim = 64 n_cams),
+// one lane per corner slot; the algorithm is rig_solve_instant of at_rigpose.h, which
+// at_rig_pose_host runs with one thread holding every slot.  Each wave selects and builds
+// its own camera's slots as k_field does; a sum over all corners is the wave butterfly, one
+// LDS row per wave, a barrier, and the n_cams partials added in camera order (two LDS
+// buffers in turn: two barriers per LM iteration, one for the 27 sums of the normal
+// equations and one for the step's cost).  The butterfly halves what a lane carries at every
+// step and lane i adds value i over the cameras for its wave (at_rigpose.h): the LDS pipeline,
+// which the waves of a workgroup share, sees 32 shuffles and n_cams reads per wave and
+// 27-value sum where all-lanes-all-values would need 162 and 27 n_cams.
+// Barriers and branches: every thread of the workgroup solves the 6 x 6 system and takes the
+// accept / reject decision itself, from sums it read from LDS after the same barrier -- the
+// same bits in every thread -- so found, ok, cn < cost, lambda, the tag counts sh.m[] that
+// bound the start loop, and with them every branch around a barrier, are uniform over the
+// workgroup.  What differs per wave (its camera's tag count in the first phase, slot validity)
+// bounds only code without a barrier in it.  Thread 0 stores the record to HBM and to the
+// mapped host buffer.
+// ---------------------------------------------------------------------------
+struct RigTeam {
+  static constexpr int NC = 1;
+  static constexpr int NS = 1;
+  int tid;
+  __device__ int cam(int) const { return tid >> 6; }
+  __device__ FpWave wave() const { return FpWave{tid & 63}; }
+  __device__ bool wave_leader() const { return (tid & 63) == 0; }
+  __device__ bool leader() const { return tid == 0; }
+  __device__ void barrier() const { __syncthreads(); }
+  // The butterfly 32 .. 1 over CUR values a lane still carries: while there are several, lane i
+  // keeps the lower or the upper half (by its bit `OFF`) and adds what i ^ OFF sends of it --
+  // the pair the full butterfly adds at this step -- so the lane ends with one value, number k.
+  template <int CUR, int OFF>
+  __device__ static void halve(double* v, int lane, int& k) {
+    if constexpr (OFF >= 1) {
+      if constexpr (CUR > 1) {
+        constexpr int h = CUR / 2;
+        const bool up = (lane & OFF) != 0;
+#pragma unroll
+        for (int j = 0; j < h; j++) {
+          const double keep = up ? v[j + h] : v[j];
+          const double send = up ? v[j] : v[j + h];
+          v[j] = keep + __shfl_xor(send, OFF);
+        }
+        if (up) k += h;
+        halve<h, OFF / 2>(v, lane, k);
+      } else {
+        v[0] = v[0] + __shfl_xor(v[0], OFF);
+        halve<1, OFF / 2>(v, lane, k);
+      }
+    }
+  }
+  template <int N>
+  __device__ void wave_sums(double (*vals)[N], double* row) const {
+    static_assert(N <= 32, "one value per lane pair");
+    constexpr int P = N <= 1 ? 1 : N <= 2 ? 2 : N <= 4 ? 4 : N <= 8 ? 8 : N <= 16 ? 16 : 32;
+    double v[P];
+#pragma unroll
+    for (int i = 0; i < P; i++) v[i] = i < N ? vals[0][i] : 0.0;
+    int k = 0;
+    halve<P, 32>(v, tid & 63, k);
+    if (k < N) row[k] = v[0];  // (the lanes that hold sum k hold the same bits)
+  }
+  // lane i adds value i over the cameras in camera order; v_readlane hands it to the wave
+  template <int N>
+  __device__ void across(double (*rows)[kRigSums], int n_cams, double* out) const {
+    const int lane = tid & 63;
+    double mine = 0.0;
+    if (lane < N) {
+      mine = rows[0][lane];
+      for (int c = 1; c < n_cams; c++) mine = mine + rows[c][lane];
+    }
+#pragma unroll
+    for (int i = 0; i < N; i++)
+      out[i] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(mine), i),
+                                __builtin_amdgcn_readlane(__double2loint(mine), i));
+  }
+};
+struct RigDevSrc {
+  const RigBufs* rb;
+  int f;
+  __device__ FpDevSrc cam(int i) const {
+    const RigCamView& v = rb->view[i];
+    const uint32_t nd = v.ndets[f];
+    return {v.dets + (size_t)f * kMaxDets, (int)(nd < (uint32_t)kMaxDets ? nd : (uint32_t)kMaxDets)};
+  }
+  __device__ RigCam rigcam(int i) const { return rb->view[i].cam; }
+};
+__global__ __launch_bounds__(64 * kRigMaxCams) void k_rig(RigBufs rb, int ninstants) {
+  __shared__ RigShared sh;
+  const int f = (int)blockIdx.x;
+  if (f >= ninstants) return;
+  const RigDevSrc src = {&rb, f};
+  const RigTeam tm = {(int)threadIdx.x};
+  rig_solve_instant(tm, src, sh, rb.lay, rb.n_cams, rb.tag_size, rb.out + f, rb.hout + f);
+}
+hipError_t launch_rig(const RigBufs& rb, int ninstants, hipStream_t st) {
+  hipLaunchKernelGGL(k_rig, dim3(ninstants), dim3(64 * rb.n_cams), 0, st, rb, ninstants);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // Shared game-piece preprocessing: preprocess_image of
 // src/game_piece_detection/src/game_piece_detection_node.cu:347-379 --
 // cv::resize (INTER_LINEAR, 8UC3), BGR->RGB (3 channels) or BGR->GRAY (1),

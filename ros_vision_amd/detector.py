@@ -45,8 +45,10 @@ EXPORTS = [
     "at_preview_size", "at_preview_bgr", "at_preview_jpeg", "at_preview_jpeg_device", "at_preview_host",
     "at_preview_jpeg_host", "at_preview_stats",
     "at_set_field_layout", "at_field_poses", "at_field_pose_host", "at_robot_in_field", "at_field_stats",
+    "at_rig_create", "at_rig_solve", "at_rig_stats", "at_rig_destroy", "at_rig_pose_host",
 ]
 AT_FIELD_MAX_TAGS = 16
+AT_RIG_MAX_CAMS = 8
 AT_GP_MAX_CANDIDATES = 4096
 # at_gp_box as a numpy record (the bit-exact view of what the library wrote)
 GP_BOX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("conf", "<f4"), ("cls", "<i4")])
@@ -92,6 +94,22 @@ class AtFieldTag(C.Structure):
 class AtFieldPose(C.Structure):
     _fields_ = [("n_tags", C.c_int32), ("ids", C.c_int32 * AT_FIELD_MAX_TAGS), ("R", C.c_double * 9),
                 ("t", C.c_double * 3), ("rms_px", C.c_double), ("steps_taken", C.c_int32)]
+
+
+class AtRigExtrinsics(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+class AtRigPose(C.Structure):
+    _fields_ = [("n_tags", C.c_int32), ("n_cams_used", C.c_int32), ("tags_per_cam", C.c_int32 * AT_RIG_MAX_CAMS),
+                ("ids", (C.c_int32 * AT_FIELD_MAX_TAGS) * AT_RIG_MAX_CAMS), ("R", C.c_double * 9),
+                ("t", C.c_double * 3), ("cov", C.c_double * 36), ("rms_px", C.c_double), ("cov_valid", C.c_int32),
+                ("steps_taken", C.c_int32), ("rejected", C.c_int32), ("dropped", C.c_int32)]
+
+
+class AtRigHostCam(C.Structure):
+    _fields_ = [("dets", C.POINTER(AtDetection)), ("poses", C.POINTER(AtPose)), ("n", C.c_int32),
+                ("cam", C.POINTER(AtCamera)), ("extr", AtRigExtrinsics)]
 
 
 class AtQuadRecord(C.Structure):
@@ -142,6 +160,26 @@ class FieldPose:
     t: np.ndarray
     rms_px: float
     steps_taken: int
+
+
+@dataclass
+class RigPose:
+    """at_rig_pose: the robot in the field at one instant from the layout tags of every camera of a
+    rig, x_field = R x_robot + t, and its covariance in the order (w_x, w_y, w_z, t_x, t_y, t_z) --
+    w a small turn in the robot frame, t in the field frame (n_tags == 0: no layout tag in any
+    camera, the rest zero)."""
+    n_tags: int
+    n_cams_used: int
+    tags_per_cam: list
+    ids: list          # per camera, the ids used (ascending)
+    R: np.ndarray
+    t: np.ndarray
+    cov: np.ndarray    # [6, 6]; zeros unless cov_valid
+    cov_valid: bool
+    rms_px: float
+    steps_taken: int
+    rejected: int
+    dropped: int
 
 
 @dataclass
@@ -301,6 +339,15 @@ def load_library(path: str = LIB_PATH):
                                          C.c_int, C.c_int, C.POINTER(AtCamera), C.c_double, C.POINTER(AtFieldPose)]
         L.at_robot_in_field.argtypes = [C.POINTER(AtFieldPose), dp, dp, dp, dp]
         L.at_field_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+    if hasattr(L, "at_rig_solve"):  # (A/B builds of older sources lack the rig pose)
+        L.at_rig_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(AtRigExtrinsics), C.c_int, C.POINTER(AtFieldTag),
+                                    C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.at_rig_solve.argtypes = [C.c_void_p, C.POINTER(AtRigPose), C.c_int]
+        L.at_rig_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.at_rig_destroy.argtypes = [C.c_void_p]
+        L.at_rig_destroy.restype = None
+        L.at_rig_pose_host.argtypes = [C.POINTER(AtRigHostCam), C.c_int, C.POINTER(AtFieldTag), C.c_int, C.c_int,
+                                       C.c_double, C.POINTER(AtRigPose)]
     _LIB = L
     return L
 
@@ -719,6 +766,110 @@ def robot_in_field(field_pose, extrinsic_rotation=None, extrinsic_offset=None):
     if rc < 0:
         raise FieldPoseError("at_robot_in_field", rc)
     return R.reshape(3, 3), t
+
+
+# ---- rig pose (k_rig) ---------------------------------------------------------
+def _rig_pose(o):
+    return RigPose(n_tags=o.n_tags, n_cams_used=o.n_cams_used, tags_per_cam=[int(x) for x in o.tags_per_cam],
+                   ids=[[int(x) for x in o.ids[i][:o.tags_per_cam[i]]] for i in range(AT_RIG_MAX_CAMS)],
+                   R=np.array(list(o.R)).reshape(3, 3), t=np.array(list(o.t)), cov=np.array(list(o.cov)).reshape(6, 6),
+                   cov_valid=bool(o.cov_valid), rms_px=o.rms_px, steps_taken=o.steps_taken, rejected=o.rejected,
+                   dropped=o.dropped)
+
+
+def _rig_extrinsics(extrinsics, n):
+    """(R, t) pairs, x_robot = R x_cam + t (None: identity / zero), as at_rig_extrinsics records."""
+    extrinsics = list(extrinsics) if extrinsics is not None else [None] * n
+    arr = (AtRigExtrinsics * max(1, len(extrinsics)))()
+    for i, e in enumerate(extrinsics):
+        R, t = (np.eye(3), np.zeros(3)) if e is None else e
+        arr[i].R[:] = [float(x) for x in np.asarray(np.eye(3) if R is None else R, np.float64).reshape(9)]
+        arr[i].t[:] = [float(x) for x in np.asarray(np.zeros(3) if t is None else t, np.float64).reshape(3)]
+    return arr, len(extrinsics)
+
+
+def rig_pose_host(cameras, tags, max_hamming=0, tag_size=TAG_SIZE):
+    """at_rig_pose_host: the rig pose of one instant on the CPU -- the reference RigSolver.solve is
+    held to.  `cameras` is one (detections, poses, camera_matrix, extrinsics) per camera: the
+    frame's detections() and poses() (same order), its CameraMatrix and its (R, t) with
+    x_robot = R x_cam + t (None: identity).  Raises FieldPoseError for arguments the library
+    refuses."""
+    L = load_library()
+    cameras = list(cameras)
+    arr = (AtRigHostCam * max(1, len(cameras)))()
+    keep = []
+    ext, _n = _rig_extrinsics([c[3] for c in cameras], len(cameras))
+    for i, (dets, poses, cam, _e) in enumerate(cameras):
+        if len(dets) != len(poses):
+            raise ValueError("one pose per detection")
+        darr, n = _detection_records(dets)
+        parr = (AtPose * max(1, n))()
+        for k, p in enumerate(poses):
+            parr[k].id = int(p.id)
+            parr[k].R[:] = [float(x) for x in np.asarray(p.R, np.float64).reshape(9)]
+            parr[k].t[:] = [float(x) for x in np.asarray(p.t, np.float64).reshape(3)]
+            parr[k].err = float(p.err)
+        c = AtCamera(fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy)
+        keep.append((darr, parr, c))
+        arr[i].dets, arr[i].poses, arr[i].n = darr, parr, n
+        arr[i].cam = C.pointer(c)
+        arr[i].extr = ext[i]
+    tarr, nt = _field_tags(tags)
+    out = AtRigPose()
+    rc = L.at_rig_pose_host(arr, len(cameras), tarr, nt, int(max_hamming), float(tag_size), C.byref(out))
+    if rc < 0:
+        raise FieldPoseError("at_rig_pose_host", rc)
+    return _rig_pose(out)
+
+
+class RigSolver:
+    """at_rig: one robot pose per instant from the layout tags of every member detector (one per
+    camera, all of this process and one device).  `extrinsics` is one (R, t) per detector with
+    x_robot = R x_cam + t (None: identity), `layout` the (id, R, t) triples set_field_layout takes.
+    The detectors must stay open while the solver is."""
+
+    def __init__(self, detectors, extrinsics, layout, max_hamming=0):
+        L = load_library()
+        self.detectors = list(detectors)
+        n = len(self.detectors)
+        if extrinsics is not None and len(list(extrinsics)) != n:
+            raise ValueError("one extrinsics pair per detector")
+        hs = (C.c_void_p * max(1, n))(*[getattr(d, "_h", None) for d in self.detectors])
+        ext, _n = _rig_extrinsics(extrinsics, n)
+        tarr, nt = _field_tags(layout)
+        h = C.c_void_p()
+        self._h = None
+        rc = L.at_rig_create(hs, ext, n, tarr, nt, int(max_hamming), C.byref(h))
+        if rc < 0:
+            raise FieldPoseError("at_rig_create", rc)
+        self._h = h
+        self._cap = max(d.max_batch for d in self.detectors)
+        self._buf = (AtRigPose * self._cap)()
+
+    def solve(self, cap=None):
+        """at_rig_solve: one RigPose per instant of the members' last batches (pending or
+        collected; the members are not collected)."""
+        cap = self._cap if cap is None else min(int(cap), self._cap)
+        rc = load_library().at_rig_solve(self._h, self._buf, cap)
+        if rc < 0:
+            raise FieldPoseError("at_rig_solve", rc)
+        self.instants = rc
+        return [_rig_pose(b) for b in self._buf[:min(rc, cap)]]
+
+    def stats(self):
+        """at_rig_stats of the last solve."""
+        buf = (C.c_uint64 * 5)()
+        n = _check(load_library().at_rig_stats(self._h, buf, len(buf)), "at_rig_stats")
+        names = ("instants_solved", "tags_used", "dropped", "rejected_steps", "kernel_ns")
+        return {k: int(v) for k, v in zip(names[:n], buf)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().at_rig_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
 
 
 def _check(rc, what):

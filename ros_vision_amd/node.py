@@ -31,7 +31,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .detector import (AT_FMT_BGR8, AT_FMT_GRAY8, AT_FMT_YUYV, TAG_SIZE, CameraMatrix, DistCoeffs, GpuDetector,
-                       robot_in_field, tag_detections)
+                       RigSolver, robot_in_field, tag_detections)
 
 PARAMETER_DEFAULTS = {
     "topic_name": "camera/image_raw",
@@ -87,15 +87,38 @@ def load_extrinsics(system_config_path, camera_serial):
             location)
 
 
+# WPILib's tag frame (x out of the face, z up, y by right-handedness) to at_pose's (x right, y
+# down, z into the tag): the columns are at_pose's x, y, z axes in WPILib's frame,
+# x_at = +y_wpi, y_at = -z_wpi, z_at = -x_wpi.  (The WPILib convention is written from memory,
+# not checked against WPILib: DESIGN 7h.)
+WPILIB_TAG_AXES = np.array([[0.0, 0.0, -1.0], [1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])
+
+
+def _quat_rotation(w, x, y, z):
+    n = np.sqrt(w * w + x * x + y * y + z * z)
+    w, x, y, z = w / n, x / n, y / n, z / n
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _wpilib_tag(g):
+    tr, q = g["pose"]["translation"], g["pose"]["rotation"]["quaternion"]
+    R = _quat_rotation(float(q["W"]), float(q["X"]), float(q["Y"]), float(q["Z"])) @ WPILIB_TAG_AXES
+    return g["ID"], R, [tr["x"], tr["y"], tr["z"]]
+
+
 def load_field_layout(layout):
     """A field layout -- where each tag stands on the field, x_field = R x_tag + t, the tag frame
     being at_pose's -- as a list of (id, R 3x3, t 3): from such a list, or from the path of a JSON
-    file {"tags": [{"id": 4, "R": [r00 .. r22], "t": [tx, ty, tz]}, ...]} (this project's own
-    format; WPILib's field layout files and their tag-frame convention are not read)."""
+    file, either this project's own {"tags": [{"id": 4, "R": [r00 .. r22], "t": [tx, ty, tz]}, ...]}
+    or a WPILib field layout {"tags": [{"ID": 4, "pose": {"translation": {"x", "y", "z"},
+    "rotation": {"quaternion": {"W", "X", "Y", "Z"}}}}, ...], "field": ...}, whose tag frame is
+    turned into at_pose's (WPILIB_TAG_AXES).  The tag size is the detector's, not the file's."""
     if isinstance(layout, (str, os.PathLike)):
         with open(layout) as f:
             data = json.load(f)
-        layout = [(g["id"], g["R"], g["t"]) for g in data["tags"]]
+        layout = [_wpilib_tag(g) if "ID" in g else (g["id"], g["R"], g["t"]) for g in data["tags"]]
     return [(int(tid), np.array(R, np.float64).reshape(3, 3), np.array(t, np.float64).reshape(3))
             for tid, R, t in layout]
 
@@ -407,3 +430,33 @@ class ApriltagsDetectorNode:
                                                        us(pp1, pc1), us(pc1, pi1), us(nt0, nt1), us(start, pi1)))
             self.csv.flush()
         return res
+
+
+
+class RigPoseFuser:
+    """One robot pose per instant from every camera of the robot: a RigSolver over the detectors
+    and loaded extrinsics of several ApriltagsDetectorNodes (all of this process, one device).
+    After the nodes' image_callbacks for one instant, publish() solves and sends (R, t, cov) --
+    x_field = R x_robot + t, cov 6 x 6 in (w, t) order (RigPose) -- on
+    <publish_pose_to_topic>/rig of the first node; an instant without a layout tag sends nothing."""
+
+    def __init__(self, camera_nodes, field_layout, max_hamming=0, publishers=None):
+        self.nodes = list(camera_nodes)
+        self.field_layout = load_field_layout(field_layout)
+        self.solver = RigSolver([n.detector for n in self.nodes],
+                                [(n.extrinsic_rotation, n.extrinsic_offset) for n in self.nodes],
+                                self.field_layout, max_hamming)
+        self.publishers = publishers if publishers is not None else self.nodes[0].publishers
+        self.rig_pose_topic = self.nodes[0].pose_topic + "/rig"
+
+    def close(self):
+        self.solver.close()
+
+    def publish(self):
+        """The RigPose of the instant the nodes last saw (published when it has a tag)."""
+        pose = self.solver.solve()[0]
+        if pose.n_tags:
+            fn = self.publishers.get(self.rig_pose_topic)
+            if fn is not None:
+                fn((pose.R, pose.t, pose.cov))
+        return pose
