@@ -669,6 +669,73 @@ void at_rig_destroy(at_rig *r);
 int at_rig_pose_host(const at_rig_host_cam *cams, int n_cams, const at_field_tag *tags, int n_tags,
                      int max_hamming, double tag_size, at_rig_pose *out);
 
+/* Rig calibration: the cameras' extrinsics from recorded instants (bundle adjustment).
+ *
+ * Unknowns: the robot's field pose at every stored instant and, per camera, the rotation
+ * (free_rot) and / or translation (free_trans) of its extrinsics x_robot = R x_cam + t.  Cost: the
+ * summed squared reprojection error in pixels of every selected layout-tag corner of every camera
+ * at every instant, projected as the rig pose does.  Parameters: per instant (w, dt) as the rig
+ * pose; per camera (we, de) with R' = R dR(we), t' = t + de.  16 Levenberg-Marquardt iterations on
+ * the whole problem through the Schur complement of the pose blocks, lambda from 1e-3, / 10
+ * (floor 1e-9) on an accepted step (the total cost fell), x 10 on a rejected one; a reduced system
+ * without a Cholesky factor is a rejected iteration.  Every instant starts from the rig pose
+ * under the initial extrinsics; one that gets none (n_tags = 0) is skipped.
+ *
+ * at_rigcal_create: AT_E_INVALID for n_cams outside 2..AT_RIG_MAX_CAMS, no camera with both
+ * flags 0 (the robot frame would float), no flag set at all, a layout at_set_field_layout would
+ * refuse, max_hamming < 0, tag_size not positive, an R that is no rotation (the layout's bound).
+ * at_rigcal_add: one instant, frames[c] the at_detections / at_poses arrays of camera c's frame;
+ * per camera the rig pose's selection is stored (at most AT_FIELD_MAX_TAGS tags: id, corners, the
+ * tag's own pose).  Returns 1 if stored, 0 if fewer than two cameras had a selected tag (such an
+ * instant constrains no extrinsic), AT_E_CAPACITY beyond AT_RIGCAL_MAX_INSTANTS.
+ * at_rigcal_solve: the solve on the GPU (kernels k_cal_*, on a stream of the calibrator's own; one
+ * synchronisation, at the end).  at_rigcal_solve_host: the same on the CPU, the kernels'
+ * arithmetic in the kernels' order: bit-equal records.  Both AT_E_INVALID without a stored
+ * instant.  cov is sigma^2 times camera c's 6 x 6 block of the inverse of the undamped reduced
+ * matrix at the final state, order (we, de), sigma^2 = cost / (2 corners - 6 instants_used - free
+ * parameters); rows and columns of parameters that are not free are zero; cov_valid = 0 (and
+ * zeros) without a factor or with a denominator that is not positive.
+ * at_rigcal_instants: per stored instant of the last solve, its final robot pose and RMS
+ * (used = 0: skipped, rest zero); returns the count, writes at most cap.
+ * at_rigcal_stats, the last solve: [0] instants used, [1] skipped, [2] accepted steps,
+ * [3] rejected steps, [4] the kernels' time in nanoseconds (HIP events around the sequence of the
+ * last at_rigcal_solve while at_rigcal_set_profiling is on, 0 otherwise). */
+#define AT_RIGCAL_MAX_INSTANTS 4096
+typedef struct {
+  at_camera cam;
+  at_rig_extrinsics extr;              /* the initial extrinsics */
+  int32_t free_rot, free_trans;
+} at_rigcal_camera;
+typedef struct { const at_detection *dets; const at_pose *poses; int32_t n; } at_rigcal_frame;
+typedef struct {
+  double R[9]; double t[3];            /* x_robot = R x_cam + t */
+  double cov[36];
+} at_rigcal_camera_result;
+typedef struct {
+  double rms_before, rms_after;        /* pixels, over the corners of the instants used */
+  int32_t instants_used, instants_skipped;
+  int32_t accepted, rejected;
+  int32_t cov_valid, n_cams;
+  at_rigcal_camera_result cams[AT_RIG_MAX_CAMS];
+} at_rigcal_result;
+typedef struct {
+  double R[9]; double t[3];            /* x_field = R x_robot + t */
+  double rms_px;
+  int32_t n_tags, used;
+} at_rigcal_instant;
+typedef struct at_rigcal at_rigcal;
+int at_rigcal_create(const at_rigcal_camera *cams, int n_cams, const at_field_tag *tags, int n_tags,
+                     int max_hamming, double tag_size, at_rigcal **out);
+int at_rigcal_add(at_rigcal *c, const at_rigcal_frame *frames);
+int at_rigcal_count(const at_rigcal *c);
+int at_rigcal_clear(at_rigcal *c);
+int at_rigcal_solve(at_rigcal *c, at_rigcal_result *out);
+int at_rigcal_solve_host(at_rigcal *c, at_rigcal_result *out);
+int at_rigcal_instants(const at_rigcal *c, at_rigcal_instant *out, int cap);
+int at_rigcal_set_profiling(at_rigcal *c, int on);
+int at_rigcal_stats(const at_rigcal *c, uint64_t *out, int cap);
+void at_rigcal_destroy(at_rigcal *c);
+
 /* Page-locked host memory (hipHostMalloc) for buffers the detector copies into on
  * its stream by DMA, e.g. at_annotate_staged's bgr_out: a pageable destination
  * goes through the runtime's staging buffers instead.  (No counterpart in the

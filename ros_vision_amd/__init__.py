@@ -12,7 +12,8 @@ from .detector import (AT_FMT_BGR8, AT_FMT_GRAY8, AT_FMT_YUYV, TAG_SIZE, TEST_CA
                        AT_GP_MAX_CANDIDATES, GP_BOX_DTYPE, GamePieceBox, GamePieceCapacityError, game_piece_boxes,
                        game_piece_parse_host, preview_host, preview_jpeg_host, preview_size,
                        FieldPose, FieldPoseError, field_pose_host, robot_in_field,
-                       AT_RIG_MAX_CAMS, RigPose, RigSolver, rig_pose_host)
+                       AT_RIG_MAX_CAMS, RigPose, RigSolver, rig_pose_host,
+                       AT_RIGCAL_MAX_INSTANTS, RigCalibration, RigCalibrator, RigCalInstant)
 
 __all__ = ["GpuDetector", "CameraMatrix", "DistCoeffs", "Detection", "Pose", "TagDetection", "load_library",
            "family_entries", "tag_detections", "game_piece_preprocess_device", "TAG_SIZE", "TEST_CAMERA", "TEST_DIST",
@@ -21,4 +22,5 @@ __all__ = ["GpuDetector", "CameraMatrix", "DistCoeffs", "Detection", "Pose", "Ta
            "GamePieceBox", "GamePieceCapacityError", "game_piece_parse_host", "game_piece_boxes", "GP_BOX_DTYPE",
            "AT_GP_MAX_CANDIDATES", "preview_size", "preview_host", "preview_jpeg_host",
            "FieldPose", "FieldPoseError", "field_pose_host", "robot_in_field",
-           "AT_RIG_MAX_CAMS", "RigPose", "RigSolver", "rig_pose_host"]
+           "AT_RIG_MAX_CAMS", "RigPose", "RigSolver", "rig_pose_host",
+           "AT_RIGCAL_MAX_INSTANTS", "RigCalibration", "RigCalibrator", "RigCalInstant"]

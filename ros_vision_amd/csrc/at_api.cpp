@@ -25,6 +25,7 @@
 #include "at_mjpg.h"
 #include "at_mjpg_entropy.h"
 #include "at_preview.h"
+#include "at_rigcal.h"
 
 namespace at {
 hipError_t launch_tap_sizes(const uint8_t* thr, const uint32_t* par, const uint32_t* size, uint32_t* out, int Wd,
@@ -55,6 +56,7 @@ bool rig_extrinsics_ok(const at_rig_extrinsics& e);
 void rig_write(const RigRecord& r, at_rig_pose* o);
 // (at_kernels.hip)
 hipError_t launch_rig(const RigBufs& rb, int ninstants, hipStream_t st);
+hipError_t launch_rigcal(const CalBufs& b, hipStream_t st);
 
 struct CodeEntry {
   int id;
@@ -2281,6 +2283,173 @@ int at_rig_stats(at_rig* r, uint64_t* out, int cap) {
   const int n = std::min(cap, 5);
   for (int i = 0; i < n; i++) out[i] = v[i];
   return n;
+}
+
+// ---- rig calibration -----------------------------------------------------------
+// The device side of an at_rigcal (at_rigcal.cpp holds the rest): a stream and two events of its
+// own, the layout and the stored instants in HBM, the solve's buffers sized for the instants
+// stored so far (grown by doubling), and pinned host memory for what comes back.
+namespace at {
+struct CalGpu {
+  int device;
+  hipStream_t st;
+  hipEvent_t ev[2];
+  int cap_n;  // instants the buffers hold
+  std::vector<void*> dev, host;
+  CalBufs b;  // device pointers
+  CalPose *h_pose[2], *h_ext[2];
+  double *h_instcost, *h_cov;
+  int32_t* h_ntags;
+  CalCtl* h_ctl;
+};
+}  // namespace at
+
+static void calgpu_release(CalGpu* g) {
+  for (void* p : g->dev) (void)hipFree(p);
+  for (void* p : g->host) (void)hipHostFree(p);
+  g->dev.clear();
+  g->host.clear();
+  g->cap_n = 0;
+}
+
+static void calgpu_free(CalGpu* g) {
+  if (!g) return;
+  (void)hipSetDevice(g->device);
+  if (g->st) (void)hipStreamSynchronize(g->st);
+  calgpu_release(g);
+  for (hipEvent_t e : g->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (g->st) (void)hipStreamDestroy(g->st);
+  delete g;
+}
+
+static int calgpu_reserve(at_rigcal* c, CalGpu* g, int n) {
+  if (hipStreamSynchronize(g->st) != hipSuccess) return AT_E_HIP;
+  calgpu_release(g);
+  bool ok = true;
+  auto dmal = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (!ok || hipMalloc(&p, bytes) != hipSuccess) {
+      ok = false;
+      return nullptr;
+    }
+    g->dev.push_back(p);
+    return p;
+  };
+  auto hmal = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (!ok || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+      ok = false;
+      return nullptr;
+    }
+    g->host.push_back(p);
+    return p;
+  };
+  CalBufs& b = g->b;
+  memset(&b, 0, sizeof(b));
+  b.n_cams = c->n_cams;
+  b.N = n;
+  const size_t N = (size_t)n, nc = (size_t)c->n_cams, E = (size_t)b.E();
+  b.obs = (const CalCamObs*)dmal(N * nc * sizeof(CalCamObs));
+  b.rec = (RigRecord*)dmal(N * sizeof(RigRecord));
+  b.ntags = (int32_t*)dmal(N * sizeof(int32_t));
+  for (int q = 0; q < 2; q++) {
+    b.pose[q] = (CalPose*)dmal(N * sizeof(CalPose));
+    b.ext[q] = (CalPose*)dmal(nc * sizeof(CalPose));
+    g->h_pose[q] = (CalPose*)hmal(N * sizeof(CalPose));
+    g->h_ext[q] = (CalPose*)hmal(nc * sizeof(CalPose));
+  }
+  b.inst = (double*)dmal(N * (size_t)b.inst_len() * sizeof(double));
+  b.part = (double*)dmal(N * E * sizeof(double));
+  b.chunk = (double*)dmal((size_t)b.chunks() * E * sizeof(double));
+  b.dc = (double*)dmal((size_t)b.M() * sizeof(double));
+  b.instcost = (double*)dmal(N * sizeof(double));
+  b.cov = (double*)dmal(nc * 36 * sizeof(double));
+  b.ctl = (CalCtl*)dmal(sizeof(CalCtl));
+  b.lay.lut = (const int16_t*)dmal(kFpMaxIds * sizeof(int16_t));
+  b.lay.tags = (const FpTag*)dmal(c->tags.size() * sizeof(FpTag));
+  b.lay.max_hamming = c->max_hamming;
+  g->h_instcost = (double*)hmal(N * sizeof(double));
+  g->h_cov = (double*)hmal(nc * 36 * sizeof(double));
+  g->h_ntags = (int32_t*)hmal(N * sizeof(int32_t));
+  g->h_ctl = (CalCtl*)hmal(sizeof(CalCtl));
+  if (!ok) {
+    calgpu_release(g);
+    return AT_E_NOMEM;
+  }
+  if (hipMemcpy((void*)b.lay.lut, c->lut.data(), kFpMaxIds * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((void*)b.lay.tags, c->tags.data(), c->tags.size() * sizeof(FpTag), hipMemcpyHostToDevice) !=
+          hipSuccess) {
+    calgpu_release(g);
+    return AT_E_HIP;
+  }
+  g->cap_n = n;
+  c->obs_dirty = true;
+  return AT_OK;
+}
+
+int at_rigcal_solve(at_rigcal* c, at_rigcal_result* out) {
+  if (!c || !out || c->n < 1) return AT_E_INVALID;
+  CalGpu* g = c->gpu;
+  if (!g) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return AT_E_HIP;
+    g = new CalGpu();
+    g->device = dev;
+    bool ok = hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; i < 2 && ok; i++) ok = hipEventCreateWithFlags(&g->ev[i], kTimingEventFlags) == hipSuccess;
+    if (!ok) {
+      calgpu_free(g);
+      return AT_E_HIP;
+    }
+    c->gpu = g;
+    c->gpu_free = calgpu_free;
+  }
+  if (hipSetDevice(g->device) != hipSuccess) return AT_E_HIP;
+  if (c->n > g->cap_n) {
+    const int rc = calgpu_reserve(c, g, std::min(kCalMaxInstants, std::max(c->n, 2 * g->cap_n)));
+    if (rc != AT_OK) return rc;
+  }
+  // (the buffers may hold more instants than are stored: the strides depend on n_cams only)
+  CalBufs b = g->b;
+  const FpLayout lay = b.lay;
+  cal_fill_bufs(*c, &b);
+  b.lay = lay;
+  const size_t N = (size_t)c->n, nc = (size_t)c->n_cams;
+  if (c->obs_dirty) {
+    HIPCHK(hipMemcpyAsync((void*)b.obs, c->obs.data(), N * nc * sizeof(CalCamObs), hipMemcpyHostToDevice, g->st));
+    c->obs_dirty = false;
+  }
+  for (size_t i = 0; i < nc; i++) {
+    memcpy(g->h_ext[0][i].R, c->cams[i].extr.R, sizeof(g->h_ext[0][i].R));
+    memcpy(g->h_ext[0][i].t, c->cams[i].extr.t, sizeof(g->h_ext[0][i].t));
+  }
+  for (int q = 0; q < 2; q++)
+    HIPCHK(hipMemcpyAsync(b.ext[q], g->h_ext[0], nc * sizeof(CalPose), hipMemcpyHostToDevice, g->st));
+  HIPCHK(hipMemsetAsync(b.ctl, 0, sizeof(CalCtl), g->st));
+  if (c->profiling) HIPCHK(hipEventRecord(g->ev[0], g->st));
+  HIPCHK(launch_rigcal(b, g->st));
+  if (c->profiling) HIPCHK(hipEventRecord(g->ev[1], g->st));
+  // (h_ext[0] is read by the copies above, which the kernels and so these copies follow in order)
+  HIPCHK(hipMemcpyAsync(g->h_ctl, b.ctl, sizeof(CalCtl), hipMemcpyDeviceToHost, g->st));
+  for (int q = 0; q < 2; q++) {
+    HIPCHK(hipMemcpyAsync(g->h_ext[q], b.ext[q], nc * sizeof(CalPose), hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipMemcpyAsync(g->h_pose[q], b.pose[q], N * sizeof(CalPose), hipMemcpyDeviceToHost, g->st));
+  }
+  HIPCHK(hipMemcpyAsync(g->h_cov, b.cov, nc * 36 * sizeof(double), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(g->h_instcost, b.instcost, N * sizeof(double), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(g->h_ntags, b.ntags, N * sizeof(int32_t), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipStreamSynchronize(g->st));
+  uint64_t ns = 0;
+  if (c->profiling) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
+    ns = (uint64_t)((double)ms * 1e6);
+  }
+  const int w = g->h_ctl->which & 1;
+  cal_finish(c, *g->h_ctl, g->h_ext[w], g->h_cov, g->h_pose[w], g->h_instcost, g->h_ntags, out);
+  c->ns = ns;
+  return AT_OK;
 }
 
 int at_gp_tensor(at_detector* d, int frame, const float** dev_ptr) {

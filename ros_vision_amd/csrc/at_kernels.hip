@@ -29,6 +29,7 @@
 #include "at_mjpg.h"
 #include "at_mjpg_entropy.h"
 #include "at_pose.h"
+#include "at_rigcal.h"
 
 
 namespace at {
@@ -6103,6 +6104,83 @@ __global__ __launch_bounds__(64 * kRigMaxCams) void k_rig(RigBufs rb, int ninsta
 }
 hipError_t launch_rig(const RigBufs& rb, int ninstants, hipStream_t st) {
   hipLaunchKernelGGL(k_rig, dim3(ninstants), dim3(64 * rb.n_cams), 0, st, rb, ninstants);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Rig calibration (at_rigcal_solve): the cameras' extrinsics from N stored instants; the
+// algorithm is at_rigcal.h's, which at_rigcal_solve_host runs with one thread.  The per-instant
+// kernels (k_cal_start, k_cal_accum, k_cal_back) are one workgroup per instant, one wave per
+// camera, one lane per corner slot, like k_rig: a camera's sums are its wave's halving butterfly
+// into its LDS row (27 + 27 + 18 + 18 values: four passes of at most kRigSums), and cross the
+// cameras in camera order after a barrier.  An instant's part of the reduced system goes to HBM
+// (b.part); k_cal_chunk adds the instants of a chunk, one thread per (chunk, entry); k_cal_reduced
+// and k_cal_decide are one workgroup each: the chunk sums in chunk order, the Cholesky factor
+// with one thread per entry of a column, and the accept / reject word (CalCtl::which) that the
+// next iteration's kernels read from HBM.  Branches around barriers depend on b.ntags[i],
+// CalCtl and the sizes only: uniform over a workgroup.
+// ---------------------------------------------------------------------------
+struct CalTeam : RigTeam {
+  int nt;
+  __device__ int first() const { return tid; }
+  __device__ int stride() const { return nt; }
+};
+__device__ inline CalTeam cal_team() {
+  CalTeam tm;
+  tm.tid = (int)threadIdx.x;
+  tm.nt = (int)blockDim.x;
+  return tm;
+}
+__global__ __launch_bounds__(64 * kRigMaxCams) void k_cal_start(CalBufs b) {
+  __shared__ RigShared sh;
+  const int i = (int)blockIdx.x;
+  if (i >= b.N) return;
+  cal_start(cal_team(), sh, b, i);
+}
+__global__ __launch_bounds__(64 * kRigMaxCams) void k_cal_accum(CalBufs b, int final) {
+  __shared__ CalShared sh;
+  const int i = (int)blockIdx.x;
+  if (i >= b.N) return;
+  cal_accum(cal_team(), sh, b, i, final != 0);
+}
+__global__ __launch_bounds__(256) void k_cal_chunk(CalBufs b) {
+  const int E = b.E();
+  const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x), ch = (int)blockIdx.y;
+  if (e >= E || ch >= b.chunks()) return;
+  cal_chunk_entry(b, ch, e);
+}
+__global__ __launch_bounds__(256) void k_cal_reduced(CalBufs b, int final) {
+  __shared__ CalSolveShared sh;
+  cal_reduced(cal_team(), sh, b, final != 0);
+}
+__global__ __launch_bounds__(64 * kRigMaxCams) void k_cal_back(CalBufs b, int step) {
+  __shared__ CalShared sh;
+  const int i = (int)blockIdx.x;
+  if (i >= b.N) return;
+  cal_back(cal_team(), sh, b, i, step != 0);
+}
+__global__ __launch_bounds__(256) void k_cal_decide(CalBufs b, int step) {
+  __shared__ CalSolveShared sh;
+  cal_decide(cal_team(), sh, b, step != 0);
+}
+// the whole solve, in order on st: start, the start's cost, kCalIters iterations, the covariance
+// pass and the final per-instant costs
+hipError_t launch_rigcal(const CalBufs& b, hipStream_t st) {
+  const dim3 per_instant(b.N), team(64 * b.n_cams);
+  const dim3 chunk_grid((b.E() + 255) / 256, b.chunks());
+  hipLaunchKernelGGL(k_cal_start, per_instant, team, 0, st, b);
+  hipLaunchKernelGGL(k_cal_back, per_instant, team, 0, st, b, 0);
+  hipLaunchKernelGGL(k_cal_decide, dim3(1), dim3(256), 0, st, b, 0);
+  for (int it = 0; it <= kCalIters; it++) {
+    const int final = it == kCalIters;
+    hipLaunchKernelGGL(k_cal_accum, per_instant, team, 0, st, b, final);
+    hipLaunchKernelGGL(k_cal_chunk, chunk_grid, dim3(256), 0, st, b);
+    hipLaunchKernelGGL(k_cal_reduced, dim3(1), dim3(256), 0, st, b, final);
+    if (final) break;
+    hipLaunchKernelGGL(k_cal_back, per_instant, team, 0, st, b, 1);
+    hipLaunchKernelGGL(k_cal_decide, dim3(1), dim3(256), 0, st, b, 1);
+  }
+  hipLaunchKernelGGL(k_cal_back, per_instant, team, 0, st, b, 0);
   return hipGetLastError();
 }
 

@@ -46,7 +46,10 @@ EXPORTS = [
     "at_preview_jpeg_host", "at_preview_stats",
     "at_set_field_layout", "at_field_poses", "at_field_pose_host", "at_robot_in_field", "at_field_stats",
     "at_rig_create", "at_rig_solve", "at_rig_stats", "at_rig_destroy", "at_rig_pose_host",
+    "at_rigcal_create", "at_rigcal_add", "at_rigcal_count", "at_rigcal_clear", "at_rigcal_solve",
+    "at_rigcal_solve_host", "at_rigcal_instants", "at_rigcal_set_profiling", "at_rigcal_stats", "at_rigcal_destroy",
 ]
+AT_RIGCAL_MAX_INSTANTS = 4096
 AT_FIELD_MAX_TAGS = 16
 AT_RIG_MAX_CAMS = 8
 AT_GP_MAX_CANDIDATES = 4096
@@ -110,6 +113,29 @@ class AtRigPose(C.Structure):
 class AtRigHostCam(C.Structure):
     _fields_ = [("dets", C.POINTER(AtDetection)), ("poses", C.POINTER(AtPose)), ("n", C.c_int32),
                 ("cam", C.POINTER(AtCamera)), ("extr", AtRigExtrinsics)]
+
+
+class AtRigcalCamera(C.Structure):
+    _fields_ = [("cam", AtCamera), ("extr", AtRigExtrinsics), ("free_rot", C.c_int32), ("free_trans", C.c_int32)]
+
+
+class AtRigcalFrame(C.Structure):
+    _fields_ = [("dets", C.POINTER(AtDetection)), ("poses", C.POINTER(AtPose)), ("n", C.c_int32)]
+
+
+class AtRigcalCameraResult(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("cov", C.c_double * 36)]
+
+
+class AtRigcalResult(C.Structure):
+    _fields_ = [("rms_before", C.c_double), ("rms_after", C.c_double), ("instants_used", C.c_int32),
+                ("instants_skipped", C.c_int32), ("accepted", C.c_int32), ("rejected", C.c_int32),
+                ("cov_valid", C.c_int32), ("n_cams", C.c_int32), ("cams", AtRigcalCameraResult * AT_RIG_MAX_CAMS)]
+
+
+class AtRigcalInstant(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("rms_px", C.c_double), ("n_tags", C.c_int32),
+                ("used", C.c_int32)]
 
 
 class AtQuadRecord(C.Structure):
@@ -180,6 +206,33 @@ class RigPose:
     steps_taken: int
     rejected: int
     dropped: int
+
+
+@dataclass
+class RigCalibration:
+    """at_rigcal_result: per camera the calibrated extrinsics x_robot = R x_cam + t and the 6 x 6
+    covariance of (we, de) -- we a small turn in the camera frame, de in the robot frame; rows and
+    columns of parameters that were not free are zero."""
+    R: list            # per camera [3, 3]
+    t: list            # per camera [3]
+    cov: list          # per camera [6, 6]; zeros unless cov_valid
+    cov_valid: bool
+    rms_before: float
+    rms_after: float
+    instants_used: int
+    instants_skipped: int
+    accepted: int
+    rejected: int
+
+
+@dataclass
+class RigCalInstant:
+    """at_rigcal_instant: a stored instant's final robot pose and RMS (used False: skipped)."""
+    R: np.ndarray
+    t: np.ndarray
+    rms_px: float
+    n_tags: int
+    used: bool
 
 
 @dataclass
@@ -348,6 +401,19 @@ def load_library(path: str = LIB_PATH):
         L.at_rig_destroy.restype = None
         L.at_rig_pose_host.argtypes = [C.POINTER(AtRigHostCam), C.c_int, C.POINTER(AtFieldTag), C.c_int, C.c_int,
                                        C.c_double, C.POINTER(AtRigPose)]
+    if hasattr(L, "at_rigcal_solve"):  # (A/B builds of older sources lack the rig calibration)
+        L.at_rigcal_create.argtypes = [C.POINTER(AtRigcalCamera), C.c_int, C.POINTER(AtFieldTag), C.c_int, C.c_int,
+                                       C.c_double, C.POINTER(C.c_void_p)]
+        L.at_rigcal_add.argtypes = [C.c_void_p, C.POINTER(AtRigcalFrame)]
+        for name in ("at_rigcal_count", "at_rigcal_clear"):
+            getattr(L, name).argtypes = [C.c_void_p]
+        for name in ("at_rigcal_solve", "at_rigcal_solve_host"):
+            getattr(L, name).argtypes = [C.c_void_p, C.POINTER(AtRigcalResult)]
+        L.at_rigcal_instants.argtypes = [C.c_void_p, C.POINTER(AtRigcalInstant), C.c_int]
+        L.at_rigcal_set_profiling.argtypes = [C.c_void_p, C.c_int]
+        L.at_rigcal_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.at_rigcal_destroy.argtypes = [C.c_void_p]
+        L.at_rigcal_destroy.restype = None
     _LIB = L
     return L
 
@@ -866,6 +932,127 @@ class RigSolver:
     def close(self):
         if getattr(self, "_h", None):
             load_library().at_rig_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+# ---- rig calibration (k_cal_*) --------------------------------------------------
+def _pose_records(poses, n):
+    parr = (AtPose * max(1, n))()
+    for k, p in enumerate(poses):
+        parr[k].id = int(p.id)
+        parr[k].R[:] = [float(x) for x in np.asarray(p.R, np.float64).reshape(9)]
+        parr[k].t[:] = [float(x) for x in np.asarray(p.t, np.float64).reshape(3)]
+        parr[k].err = float(p.err)
+    return parr
+
+
+class RigCalibrator:
+    """at_rigcal: the cameras' extrinsics from recorded instants.  `cameras` is one
+    (camera_matrix, (R, t), free_rot, free_trans) per camera -- its CameraMatrix, its initial
+    extrinsics x_robot = R x_cam + t (None: identity) and which of the two are to be solved for;
+    at least one camera must have both held fixed.  `layout` is the (id, R, t) triples
+    set_field_layout takes.  Raises FieldPoseError for arguments the library refuses."""
+
+    def __init__(self, cameras, layout, max_hamming=0, tag_size=TAG_SIZE):
+        L = load_library()
+        cameras = list(cameras)
+        self.n_cams = n = len(cameras)
+        arr = (AtRigcalCamera * max(1, n))()
+        ext, _n = _rig_extrinsics([c[1] for c in cameras], n)
+        for i, (cam, _e, free_rot, free_trans) in enumerate(cameras):
+            arr[i].cam = AtCamera(fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy)
+            arr[i].extr = ext[i]
+            arr[i].free_rot, arr[i].free_trans = int(bool(free_rot)), int(bool(free_trans))
+        tarr, nt = _field_tags(layout)
+        h = C.c_void_p()
+        self._h = None
+        rc = L.at_rigcal_create(arr, n, tarr, nt, int(max_hamming), float(tag_size), C.byref(h))
+        if rc < 0:
+            raise FieldPoseError("at_rigcal_create", rc)
+        self._h = h
+
+    def add(self, per_camera_results):
+        """at_rigcal_add: one instant, per camera (detections, poses) of its frame in the same
+        order (None or empty: the camera saw nothing).  True if the instant was stored, False if
+        fewer than two cameras had a layout tag.  FieldPoseError (AT_E_CAPACITY) beyond
+        AT_RIGCAL_MAX_INSTANTS."""
+        arr, _keep = self._frames(per_camera_results)
+        rc = load_library().at_rigcal_add(self._h, arr)
+        if rc < 0:
+            raise FieldPoseError("at_rigcal_add", rc)
+        return bool(rc)
+
+    def _frames(self, per_camera_results):
+        """The at_rigcal_frame array of one instant, and the records it points into."""
+        per = list(per_camera_results)
+        if len(per) != self.n_cams:
+            raise ValueError("one (detections, poses) pair per camera")
+        arr = (AtRigcalFrame * self.n_cams)()
+        keep = []
+        for i, r in enumerate(per):
+            dets, poses = r if r is not None else ((), ())
+            dets, poses = list(dets), list(poses)
+            if len(dets) != len(poses):
+                raise ValueError("one pose per detection")
+            darr, n = _detection_records(dets)
+            parr = _pose_records(poses, n)
+            keep.append((darr, parr))
+            arr[i].dets, arr[i].poses, arr[i].n = darr, parr, n
+        return arr, keep
+
+    def __len__(self):
+        return int(load_library().at_rigcal_count(self._h))
+
+    def clear(self):
+        _check(load_library().at_rigcal_clear(self._h), "at_rigcal_clear")
+
+    def _solve(self, name):
+        out = AtRigcalResult()
+        rc = getattr(load_library(), name)(self._h, C.byref(out))
+        if rc < 0:
+            raise FieldPoseError(name, rc)
+        self.record = out
+        n = out.n_cams
+        return RigCalibration(R=[np.array(list(out.cams[i].R)).reshape(3, 3) for i in range(n)],
+                              t=[np.array(list(out.cams[i].t)) for i in range(n)],
+                              cov=[np.array(list(out.cams[i].cov)).reshape(6, 6) for i in range(n)],
+                              cov_valid=bool(out.cov_valid), rms_before=out.rms_before, rms_after=out.rms_after,
+                              instants_used=out.instants_used, instants_skipped=out.instants_skipped,
+                              accepted=out.accepted, rejected=out.rejected)
+
+    def solve(self):
+        """at_rigcal_solve: the solve on the GPU (the current device), on the calibrator's own stream."""
+        return self._solve("at_rigcal_solve")
+
+    def solve_host(self):
+        """at_rigcal_solve_host: the same solve on the CPU, bit-equal records."""
+        return self._solve("at_rigcal_solve_host")
+
+    def instants(self):
+        """at_rigcal_instants: one RigCalInstant per stored instant of the last solve."""
+        L = load_library()
+        n = _check(L.at_rigcal_instants(self._h, None, 0), "at_rigcal_instants")
+        buf = (AtRigcalInstant * max(1, n))()
+        n = _check(L.at_rigcal_instants(self._h, buf, n), "at_rigcal_instants")
+        return [RigCalInstant(R=np.array(list(b.R)).reshape(3, 3), t=np.array(list(b.t)), rms_px=b.rms_px,
+                              n_tags=b.n_tags, used=bool(b.used)) for b in buf[:n]]
+
+    def set_profiling(self, on=True):
+        _check(load_library().at_rigcal_set_profiling(self._h, int(bool(on))), "at_rigcal_set_profiling")
+
+    def stats(self):
+        """at_rigcal_stats of the last solve."""
+        buf = (C.c_uint64 * 5)()
+        n = _check(load_library().at_rigcal_stats(self._h, buf, len(buf)), "at_rigcal_stats")
+        names = ("instants_used", "instants_skipped", "accepted_steps", "rejected_steps", "kernel_ns")
+        return {k: int(v) for k, v in zip(names[:n], buf)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().at_rigcal_destroy(self._h)
             self._h = None
 
     def __del__(self):

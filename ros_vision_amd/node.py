@@ -87,6 +87,23 @@ def load_extrinsics(system_config_path, camera_serial):
             location)
 
 
+def save_extrinsics(system_config_path, location, R, t):
+    """Write extrinsics.<location> of system_config.json -- "rotation" 3 x 3, "offset" 3, what
+    load_extrinsics reads back -- and leave the rest of the file as it was (a missing file is
+    created)."""
+    try:
+        with open(system_config_path) as f:
+            data = json.load(f)
+    except OSError:
+        data = {}
+    R, t = np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3)
+    data.setdefault("extrinsics", {})[location] = {"rotation": [[float(x) for x in row] for row in R],
+                                                   "offset": [float(x) for x in t]}
+    with open(system_config_path, "w") as f:
+        json.dump(data, f, indent=2)
+        f.write("\n")
+
+
 # WPILib's tag frame (x out of the face, z up, y by right-handedness) to at_pose's (x right, y
 # down, z into the tag): the columns are at_pose's x, y, z axes in WPILib's frame,
 # x_at = +y_wpi, y_at = -z_wpi, z_at = -x_wpi.  (The WPILib convention is written from memory,
@@ -438,9 +455,11 @@ class RigPoseFuser:
     and loaded extrinsics of several ApriltagsDetectorNodes (all of this process, one device).
     After the nodes' image_callbacks for one instant, publish() solves and sends (R, t, cov) --
     x_field = R x_robot + t, cov 6 x 6 in (w, t) order (RigPose) -- on
-    <publish_pose_to_topic>/rig of the first node; an instant without a layout tag sends nothing."""
+    <publish_pose_to_topic>/rig of the first node; an instant without a layout tag sends nothing.
+    With a `calibrator` (RigCalibrator over the same cameras, in the nodes' order) every fused
+    instant is also added to it, from the nodes' collected detections and poses."""
 
-    def __init__(self, camera_nodes, field_layout, max_hamming=0, publishers=None):
+    def __init__(self, camera_nodes, field_layout, max_hamming=0, publishers=None, calibrator=None):
         self.nodes = list(camera_nodes)
         self.field_layout = load_field_layout(field_layout)
         self.solver = RigSolver([n.detector for n in self.nodes],
@@ -448,6 +467,7 @@ class RigPoseFuser:
                                 self.field_layout, max_hamming)
         self.publishers = publishers if publishers is not None else self.nodes[0].publishers
         self.rig_pose_topic = self.nodes[0].pose_topic + "/rig"
+        self.calibrator = calibrator
 
     def close(self):
         self.solver.close()
@@ -459,4 +479,6 @@ class RigPoseFuser:
             fn = self.publishers.get(self.rig_pose_topic)
             if fn is not None:
                 fn((pose.R, pose.t, pose.cov))
+        if self.calibrator is not None:
+            self.calibrator.add([(n.detector.detections(0), n.detector.poses(0)) for n in self.nodes])
         return pose
