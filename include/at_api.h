@@ -736,6 +736,90 @@ int at_rigcal_set_profiling(at_rigcal *c, int on);
 int at_rigcal_stats(const at_rigcal *c, uint64_t *out, int cap);
 void at_rigcal_destroy(at_rigcal *c);
 
+/* Camera calibration: the intrinsics and distortion of one camera from views of a tag board.
+ *
+ * A board is an at_field_tag array: each tag's pose in the board frame, any rigid arrangement.
+ * Unknowns: the board's pose in every stored view (x_cam = R x_board + t) and the entries of
+ * (fx, fy, cx, cy, k1, k2, p1, p2, k3) that free_mask selects (AT_CAMCAL_FX .. AT_CAMCAL_K3);
+ * free_mask = 0 fits the view poses only, which scores an existing calibration.  Cost: the summed
+ * squared error in pixels of every stored corner against at_detection.p under the detector's
+ * forward model (x = Px/Pz, y = Py/Pz, r2 = x x + y y, lin = 1 + k1 r2 + k2 r2^2 + k3 r2^3,
+ * x'' = x lin + 2 p1 x y + p2 (r2 + 2 x x), y'' = y lin + p1 (r2 + 2 y y) + 2 p2 x y, u = fx x'' + cx,
+ * v = fy y'' + cy); a corner at Pz <= 0 costs infinity.  Record the views with the detector's
+ * distortion set to zero, so that p is the raw pixel.
+ * 30 Levenberg-Marquardt iterations on the whole problem through the Schur complement of the
+ * views' 6 x 6 pose blocks, lambda from 1e-3, / 10 (floor 1e-9) on an accepted step (the total
+ * cost fell and every Pz stayed positive), x 10 on a rejected one; a reduced 9 x 9 system without
+ * a Cholesky factor is a rejected iteration.  The pose step is the field pose's (w left-multiplied,
+ * t' = t + dt), the intrinsics step additive; a value that is not free comes back bit for bit.
+ * Start: cfg.init as given (guess = 0), or (guess = 1) fx, fy from the stored tags' homographies by
+ * Zhang's two constraints per plane with the principal point at (width / 2, height / 2) and
+ * distortion 0.  Each view starts from the stored tag whose homography pose under the start
+ * intrinsics has the least reprojection error over the view's corners; a view where every
+ * candidate has a corner behind the camera is skipped.
+ *
+ * at_camcal_create: AT_E_INVALID for a NULL, a free_mask outside 0..511, width, height or tag_size
+ * not positive, guess = 0 with init.fx or init.fy not positive, a board at_set_field_layout would
+ * refuse (or an empty one), max_hamming < 0.
+ * at_camcal_add: one frame's detections; the field pose's selection over the board's ids is stored
+ * (at most AT_FIELD_MAX_TAGS tags: id, corners, homography).  Returns 1 if a tag was stored, 0 if
+ * none, AT_E_CAPACITY beyond AT_CAMCAL_MAX_VIEWS.
+ * at_camcal_solve: the solve on the GPU (kernels k_cc_*, on a stream of the calibrator's own; one
+ * synchronisation, at the end).  at_camcal_solve_host: the same on the CPU, the kernels'
+ * arithmetic in the kernels' order: bit-equal records.  Both AT_E_INVALID without a stored view
+ * or when the focal guess has no positive solution (e.g. every view fronto-parallel).
+ * cov is sigma^2 times the inverse of the undamped reduced matrix at the final state, row-major
+ * 9 x 9 in the mask's order, sigma^2 = cost / (2 corners - 6 views_used - free parameters); rows and
+ * columns of parameters that are not free are zero; cov_valid = 0 (and zeros) without a factor or
+ * with a denominator that is not positive.
+ * at_camcal_views: per stored view of the last solve, the board's final pose and RMS (used = 0:
+ * skipped, rest zero); returns the count, writes at most cap.
+ * at_camcal_stats, the last solve: [0] views used, [1] skipped, [2] accepted steps, [3] rejected
+ * steps, [4] the kernels' time in nanoseconds (HIP events around the sequence of the last
+ * at_camcal_solve while at_camcal_set_profiling is on, 0 otherwise). */
+#define AT_CAMCAL_MAX_VIEWS 4096
+#define AT_CAMCAL_FX 1
+#define AT_CAMCAL_FY 2
+#define AT_CAMCAL_CX 4
+#define AT_CAMCAL_CY 8
+#define AT_CAMCAL_K1 16
+#define AT_CAMCAL_K2 32
+#define AT_CAMCAL_P1 64
+#define AT_CAMCAL_P2 128
+#define AT_CAMCAL_K3 256
+typedef struct {
+  int32_t width, height;
+  at_camera init;
+  int32_t free_mask;
+  int32_t guess;
+} at_camcal_config;
+typedef struct {
+  at_camera cam;
+  double cov[81];
+  double rms_before, rms_after;        /* pixels, over the corners of the views used */
+  int32_t views_used, views_skipped;
+  int32_t corners;
+  int32_t accepted, rejected;
+  int32_t cov_valid;
+} at_camcal_result;
+typedef struct {
+  double R[9]; double t[3];            /* x_cam = R x_board + t */
+  double rms_px;
+  int32_t n_tags, used;
+} at_camcal_view;
+typedef struct at_camcal at_camcal;
+int at_camcal_create(const at_camcal_config *cfg, const at_field_tag *board, int n_tags, int max_hamming,
+                     double tag_size, at_camcal **out);
+int at_camcal_add(at_camcal *c, const at_detection *dets, int n);
+int at_camcal_count(const at_camcal *c);
+int at_camcal_clear(at_camcal *c);
+int at_camcal_solve(at_camcal *c, at_camcal_result *out);
+int at_camcal_solve_host(at_camcal *c, at_camcal_result *out);
+int at_camcal_views(const at_camcal *c, at_camcal_view *out, int cap);
+int at_camcal_set_profiling(at_camcal *c, int on);
+int at_camcal_stats(const at_camcal *c, uint64_t *out, int cap);
+void at_camcal_destroy(at_camcal *c);
+
 /* Page-locked host memory (hipHostMalloc) for buffers the detector copies into on
  * its stream by DMA, e.g. at_annotate_staged's bgr_out: a pageable destination
  * goes through the runtime's staging buffers instead.  (No counterpart in the

@@ -26,6 +26,7 @@
 #include "at_mjpg_entropy.h"
 #include "at_preview.h"
 #include "at_rigcal.h"
+#include "at_camcal.h"
 
 namespace at {
 hipError_t launch_tap_sizes(const uint8_t* thr, const uint32_t* par, const uint32_t* size, uint32_t* out, int Wd,
@@ -57,6 +58,7 @@ void rig_write(const RigRecord& r, at_rig_pose* o);
 // (at_kernels.hip)
 hipError_t launch_rig(const RigBufs& rb, int ninstants, hipStream_t st);
 hipError_t launch_rigcal(const CalBufs& b, hipStream_t st);
+hipError_t launch_camcal(const CcBufs& b, hipStream_t st);
 
 struct CodeEntry {
   int id;
@@ -2448,6 +2450,172 @@ int at_rigcal_solve(at_rigcal* c, at_rigcal_result* out) {
   }
   const int w = g->h_ctl->which & 1;
   cal_finish(c, *g->h_ctl, g->h_ext[w], g->h_cov, g->h_pose[w], g->h_instcost, g->h_ntags, out);
+  c->ns = ns;
+  return AT_OK;
+}
+
+// ---- camera calibration --------------------------------------------------------
+// The device side of an at_camcal (at_camcal.cpp holds the rest), as CalGpu: a stream and two
+// events of its own, the board and the stored views in HBM, the solve's buffers sized for the
+// views stored so far (grown by doubling), and pinned host memory for what comes back.
+namespace at {
+struct CcGpu {
+  int device;
+  hipStream_t st;
+  hipEvent_t ev[2];
+  int cap_n;  // views the buffers hold
+  std::vector<void*> dev, host;
+  CcBufs b;  // device pointers
+  CalPose* h_pose[2];
+  CcCam* h_cam;  // [2]
+  double *h_viewcost, *h_cov;
+  int32_t* h_ntags;
+  CalCtl* h_ctl;
+};
+}  // namespace at
+
+static void ccgpu_release(CcGpu* g) {
+  for (void* p : g->dev) (void)hipFree(p);
+  for (void* p : g->host) (void)hipHostFree(p);
+  g->dev.clear();
+  g->host.clear();
+  g->cap_n = 0;
+}
+
+static void ccgpu_free(CcGpu* g) {
+  if (!g) return;
+  (void)hipSetDevice(g->device);
+  if (g->st) (void)hipStreamSynchronize(g->st);
+  ccgpu_release(g);
+  for (hipEvent_t e : g->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (g->st) (void)hipStreamDestroy(g->st);
+  delete g;
+}
+
+static int ccgpu_reserve(at_camcal* c, CcGpu* g, int n) {
+  if (hipStreamSynchronize(g->st) != hipSuccess) return AT_E_HIP;
+  ccgpu_release(g);
+  bool ok = true;
+  auto dmal = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (!ok || hipMalloc(&p, bytes) != hipSuccess) {
+      ok = false;
+      return nullptr;
+    }
+    g->dev.push_back(p);
+    return p;
+  };
+  auto hmal = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (!ok || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+      ok = false;
+      return nullptr;
+    }
+    g->host.push_back(p);
+    return p;
+  };
+  CcBufs& b = g->b;
+  memset(&b, 0, sizeof(b));
+  b.N = n;
+  const size_t N = (size_t)n;
+  b.obs = (const CcObs*)dmal(N * sizeof(CcObs));
+  b.ntags = (int32_t*)dmal(N * sizeof(int32_t));
+  for (int q = 0; q < 2; q++) {
+    b.pose[q] = (CalPose*)dmal(N * sizeof(CalPose));
+    b.cam[q] = (CcCam*)dmal(sizeof(CcCam));
+    g->h_pose[q] = (CalPose*)hmal(N * sizeof(CalPose));
+  }
+  b.view = (double*)dmal(N * kCcViewLen * sizeof(double));
+  b.part = (double*)dmal(N * kCcE * sizeof(double));
+  b.chunk = (double*)dmal((size_t)b.chunks() * kCcE * sizeof(double));
+  b.dc = (double*)dmal(kCcP * sizeof(double));
+  b.viewcost = (double*)dmal(N * sizeof(double));
+  b.cov = (double*)dmal(81 * sizeof(double));
+  b.ctl = (CalCtl*)dmal(sizeof(CalCtl));
+  b.lay.lut = (const int16_t*)dmal(kFpMaxIds * sizeof(int16_t));
+  b.lay.tags = (const FpTag*)dmal(c->tags.size() * sizeof(FpTag));
+  b.lay.max_hamming = c->max_hamming;
+  g->h_cam = (CcCam*)hmal(2 * sizeof(CcCam));
+  g->h_viewcost = (double*)hmal(N * sizeof(double));
+  g->h_cov = (double*)hmal(81 * sizeof(double));
+  g->h_ntags = (int32_t*)hmal(N * sizeof(int32_t));
+  g->h_ctl = (CalCtl*)hmal(sizeof(CalCtl));
+  if (!ok) {
+    ccgpu_release(g);
+    return AT_E_NOMEM;
+  }
+  if (hipMemcpy((void*)b.lay.lut, c->lut.data(), kFpMaxIds * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((void*)b.lay.tags, c->tags.data(), c->tags.size() * sizeof(FpTag), hipMemcpyHostToDevice) !=
+          hipSuccess) {
+    ccgpu_release(g);
+    return AT_E_HIP;
+  }
+  g->cap_n = n;
+  c->obs_dirty = true;
+  return AT_OK;
+}
+
+int at_camcal_solve(at_camcal* c, at_camcal_result* out) {
+  if (!c || !out || c->n < 1) return AT_E_INVALID;
+  CcCam start;
+  const int src = cc_start_camera(*c, &start);
+  if (src != AT_OK) return src;
+  CcGpu* g = c->gpu;
+  if (!g) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return AT_E_HIP;
+    g = new CcGpu();
+    g->device = dev;
+    bool ok = hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; i < 2 && ok; i++) ok = hipEventCreateWithFlags(&g->ev[i], kTimingEventFlags) == hipSuccess;
+    if (!ok) {
+      ccgpu_free(g);
+      return AT_E_HIP;
+    }
+    c->gpu = g;
+    c->gpu_free = ccgpu_free;
+  }
+  if (hipSetDevice(g->device) != hipSuccess) return AT_E_HIP;
+  if (c->n > g->cap_n) {
+    const int rc = ccgpu_reserve(c, g, std::min(kCcMaxViews, std::max(c->n, 2 * g->cap_n)));
+    if (rc != AT_OK) return rc;
+  }
+  // (the buffers may hold more views than are stored: no stride depends on the count)
+  CcBufs b = g->b;
+  b.N = c->n;
+  b.tag_size = c->tag_size;
+  b.free_mask = c->cfg.free_mask;
+  const size_t N = (size_t)c->n;
+  if (c->obs_dirty) {
+    HIPCHK(hipMemcpyAsync((void*)b.obs, c->obs.data(), N * sizeof(CcObs), hipMemcpyHostToDevice, g->st));
+    c->obs_dirty = false;
+  }
+  g->h_cam[0] = start;
+  for (int q = 0; q < 2; q++)
+    HIPCHK(hipMemcpyAsync(b.cam[q], &g->h_cam[0], sizeof(CcCam), hipMemcpyHostToDevice, g->st));
+  HIPCHK(hipMemsetAsync(b.ctl, 0, sizeof(CalCtl), g->st));
+  if (c->profiling) HIPCHK(hipEventRecord(g->ev[0], g->st));
+  HIPCHK(launch_camcal(b, g->st));
+  if (c->profiling) HIPCHK(hipEventRecord(g->ev[1], g->st));
+  // (h_cam[0] is read by the copies above, which the kernels and so these copies follow in order)
+  HIPCHK(hipMemcpyAsync(g->h_ctl, b.ctl, sizeof(CalCtl), hipMemcpyDeviceToHost, g->st));
+  for (int q = 0; q < 2; q++) {
+    HIPCHK(hipMemcpyAsync(&g->h_cam[q], b.cam[q], sizeof(CcCam), hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipMemcpyAsync(g->h_pose[q], b.pose[q], N * sizeof(CalPose), hipMemcpyDeviceToHost, g->st));
+  }
+  HIPCHK(hipMemcpyAsync(g->h_cov, b.cov, 81 * sizeof(double), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(g->h_viewcost, b.viewcost, N * sizeof(double), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(g->h_ntags, b.ntags, N * sizeof(int32_t), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipStreamSynchronize(g->st));
+  uint64_t ns = 0;
+  if (c->profiling) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
+    ns = (uint64_t)((double)ms * 1e6);
+  }
+  const int w = g->h_ctl->which & 1;
+  cc_finish(c, *g->h_ctl, g->h_cam[w], g->h_cov, g->h_pose[w], g->h_viewcost, g->h_ntags, out);
   c->ns = ns;
   return AT_OK;
 }

@@ -30,6 +30,7 @@
 #include "at_mjpg_entropy.h"
 #include "at_pose.h"
 #include "at_rigcal.h"
+#include "at_camcal.h"
 
 
 namespace at {
@@ -6181,6 +6182,72 @@ hipError_t launch_rigcal(const CalBufs& b, hipStream_t st) {
     hipLaunchKernelGGL(k_cal_decide, dim3(1), dim3(256), 0, st, b, 1);
   }
   hipLaunchKernelGGL(k_cal_back, per_instant, team, 0, st, b, 0);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Camera calibration (at_camcal_solve): one camera's intrinsics and distortion from N stored
+// views of a tag board; the algorithm is at_camcal.h's, which at_camcal_solve_host runs with one
+// thread.  The per-view kernels (k_cc_start, k_cc_accum, k_cc_back) are one workgroup of one wave
+// per view, one lane per corner slot, like k_field: a view shares nothing with another but the
+// nine intrinsics, so more views per workgroup would only tie their barriers together.  The 135
+// sums of a view cross the wave in five passes of 27 by the halving butterfly into LDS (one pass
+// holds 32 values per lane at most: no scratch); ten lanes then solve the 6 x 6 system for the
+// nine columns of W and for g, and the lanes share the 99 entries of the view's part, which goes
+// to HBM (b.part).  k_cc_chunk adds the views of a chunk, one thread per (chunk, entry);
+// k_cc_reduced and k_cc_decide are one workgroup each: the chunk sums in chunk order, the 9 x 9
+// Cholesky factor, the step, and the accept / reject word (CalCtl::which) that the next
+// iteration's kernels read from HBM.  Branches around barriers depend on b.ntags[i], CalCtl and
+// the sizes only: uniform over a workgroup.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_cc_start(CcBufs b) {
+  __shared__ CcShared sh;
+  const int i = (int)blockIdx.x;
+  if (i >= b.N) return;
+  cc_start(cal_team(), sh, b, i);
+}
+__global__ __launch_bounds__(64) void k_cc_accum(CcBufs b, int final) {
+  __shared__ CcShared sh;
+  const int i = (int)blockIdx.x;
+  if (i >= b.N) return;
+  cc_accum(cal_team(), sh, b, i, final != 0);
+}
+__global__ __launch_bounds__(128) void k_cc_chunk(CcBufs b) {
+  const int e = (int)threadIdx.x, ch = (int)blockIdx.x;
+  if (e >= kCcE || ch >= b.chunks()) return;
+  cc_chunk_entry(b, ch, e);
+}
+__global__ __launch_bounds__(128) void k_cc_reduced(CcBufs b, int final) {
+  __shared__ CcSolveShared sh;
+  cc_reduced(cal_team(), sh, b, final != 0);
+}
+__global__ __launch_bounds__(64) void k_cc_back(CcBufs b, int step) {
+  __shared__ CcShared sh;
+  const int i = (int)blockIdx.x;
+  if (i >= b.N) return;
+  cc_back(cal_team(), sh, b, i, step != 0);
+}
+__global__ __launch_bounds__(128) void k_cc_decide(CcBufs b, int step) {
+  __shared__ CcSolveShared sh;
+  cc_decide(cal_team(), sh, b, step != 0);
+}
+// the whole solve, in order on st: start, the start's cost, kCcIters iterations, the covariance
+// pass and the final per-view costs: 3 + 5 kCcIters + 3 + 1 = 157 launches
+hipError_t launch_camcal(const CcBufs& b, hipStream_t st) {
+  const dim3 per_view(b.N), wave(64), chunks(b.chunks()), one(1), team(128);
+  hipLaunchKernelGGL(k_cc_start, per_view, wave, 0, st, b);
+  hipLaunchKernelGGL(k_cc_back, per_view, wave, 0, st, b, 0);
+  hipLaunchKernelGGL(k_cc_decide, one, team, 0, st, b, 0);
+  for (int it = 0; it <= kCcIters; it++) {
+    const int final = it == kCcIters;
+    hipLaunchKernelGGL(k_cc_accum, per_view, wave, 0, st, b, final);
+    hipLaunchKernelGGL(k_cc_chunk, chunks, team, 0, st, b);
+    hipLaunchKernelGGL(k_cc_reduced, one, team, 0, st, b, final);
+    if (final) break;
+    hipLaunchKernelGGL(k_cc_back, per_view, wave, 0, st, b, 1);
+    hipLaunchKernelGGL(k_cc_decide, one, team, 0, st, b, 1);
+  }
+  hipLaunchKernelGGL(k_cc_back, per_view, wave, 0, st, b, 0);
   return hipGetLastError();
 }
 

@@ -48,8 +48,17 @@ EXPORTS = [
     "at_rig_create", "at_rig_solve", "at_rig_stats", "at_rig_destroy", "at_rig_pose_host",
     "at_rigcal_create", "at_rigcal_add", "at_rigcal_count", "at_rigcal_clear", "at_rigcal_solve",
     "at_rigcal_solve_host", "at_rigcal_instants", "at_rigcal_set_profiling", "at_rigcal_stats", "at_rigcal_destroy",
+    "at_camcal_create", "at_camcal_add", "at_camcal_count", "at_camcal_clear", "at_camcal_solve",
+    "at_camcal_solve_host", "at_camcal_views", "at_camcal_set_profiling", "at_camcal_stats", "at_camcal_destroy",
 ]
 AT_RIGCAL_MAX_INSTANTS = 4096
+AT_CAMCAL_MAX_VIEWS = 4096
+# at_camcal_config.free_mask bits, in at_camera's order
+CAMCAL_PARAMS = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")
+(AT_CAMCAL_FX, AT_CAMCAL_FY, AT_CAMCAL_CX, AT_CAMCAL_CY, AT_CAMCAL_K1, AT_CAMCAL_K2, AT_CAMCAL_P1, AT_CAMCAL_P2,
+ AT_CAMCAL_K3) = (1 << i for i in range(9))
+AT_CAMCAL_PINHOLE = AT_CAMCAL_FX | AT_CAMCAL_FY | AT_CAMCAL_CX | AT_CAMCAL_CY
+AT_CAMCAL_ALL = 511
 AT_FIELD_MAX_TAGS = 16
 AT_RIG_MAX_CAMS = 8
 AT_GP_MAX_CANDIDATES = 4096
@@ -134,6 +143,22 @@ class AtRigcalResult(C.Structure):
 
 
 class AtRigcalInstant(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("rms_px", C.c_double), ("n_tags", C.c_int32),
+                ("used", C.c_int32)]
+
+
+class AtCamcalConfig(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("init", AtCamera), ("free_mask", C.c_int32),
+                ("guess", C.c_int32)]
+
+
+class AtCamcalResult(C.Structure):
+    _fields_ = [("cam", AtCamera), ("cov", C.c_double * 81), ("rms_before", C.c_double), ("rms_after", C.c_double),
+                ("views_used", C.c_int32), ("views_skipped", C.c_int32), ("corners", C.c_int32),
+                ("accepted", C.c_int32), ("rejected", C.c_int32), ("cov_valid", C.c_int32)]
+
+
+class AtCamcalView(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("rms_px", C.c_double), ("n_tags", C.c_int32),
                 ("used", C.c_int32)]
 
@@ -228,6 +253,42 @@ class RigCalibration:
 @dataclass
 class RigCalInstant:
     """at_rigcal_instant: a stored instant's final robot pose and RMS (used False: skipped)."""
+    R: np.ndarray
+    t: np.ndarray
+    rms_px: float
+    n_tags: int
+    used: bool
+
+
+@dataclass
+class CameraCalibration:
+    """at_camcal_result: the calibrated camera as `params` (fx, fy, cx, cy, k1, k2, p1, p2, k3) and its
+    9 x 9 covariance in that order; rows and columns of parameters that were not free are zero."""
+    params: np.ndarray  # [9]
+    cov: np.ndarray     # [9, 9]; zeros unless cov_valid
+    cov_valid: bool
+    rms_before: float
+    rms_after: float
+    views_used: int
+    views_skipped: int
+    corners: int
+    accepted: int
+    rejected: int
+
+    @property
+    def camera_matrix(self):
+        return CameraMatrix(fx=float(self.params[0]), cx=float(self.params[2]), fy=float(self.params[1]),
+                            cy=float(self.params[3]))
+
+    @property
+    def distortion_coefficients(self):
+        return DistCoeffs(*[float(x) for x in self.params[4:]])
+
+
+@dataclass
+class CameraCalView:
+    """at_camcal_view: the board's final pose in a stored view, x_cam = R x_board + t, and the view's
+    RMS (used False: skipped)."""
     R: np.ndarray
     t: np.ndarray
     rms_px: float
@@ -414,6 +475,19 @@ def load_library(path: str = LIB_PATH):
         L.at_rigcal_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
         L.at_rigcal_destroy.argtypes = [C.c_void_p]
         L.at_rigcal_destroy.restype = None
+    if hasattr(L, "at_camcal_solve"):  # (A/B builds of older sources lack the camera calibration)
+        L.at_camcal_create.argtypes = [C.POINTER(AtCamcalConfig), C.POINTER(AtFieldTag), C.c_int, C.c_int, C.c_double,
+                                       C.POINTER(C.c_void_p)]
+        L.at_camcal_add.argtypes = [C.c_void_p, C.POINTER(AtDetection), C.c_int]
+        for name in ("at_camcal_count", "at_camcal_clear"):
+            getattr(L, name).argtypes = [C.c_void_p]
+        for name in ("at_camcal_solve", "at_camcal_solve_host"):
+            getattr(L, name).argtypes = [C.c_void_p, C.POINTER(AtCamcalResult)]
+        L.at_camcal_views.argtypes = [C.c_void_p, C.POINTER(AtCamcalView), C.c_int]
+        L.at_camcal_set_profiling.argtypes = [C.c_void_p, C.c_int]
+        L.at_camcal_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.at_camcal_destroy.argtypes = [C.c_void_p]
+        L.at_camcal_destroy.restype = None
     _LIB = L
     return L
 
@@ -1053,6 +1127,98 @@ class RigCalibrator:
     def close(self):
         if getattr(self, "_h", None):
             load_library().at_rigcal_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+# ---- camera calibration (k_cc_*) ------------------------------------------------
+class CameraCalibrator:
+    """at_camcal: one camera's intrinsics and distortion from views of a board of tags.  `board` is
+    the (id, R, t) triples set_field_layout takes, each tag's pose in the board frame; `free` the
+    mask of AT_CAMCAL_* bits to solve for (0: only the view poses, which scores `init`); `init` the
+    nine starting values (fx, fy, cx, cy, k1, k2, p1, p2, k3) or a (CameraMatrix, DistCoeffs) pair --
+    None: the focal lengths are guessed from the tags' homographies, the principal point starts at
+    the frame's centre and the distortion at zero.  Feed it detections made with zero distortion.
+    Raises FieldPoseError for arguments the library refuses."""
+
+    def __init__(self, width, height, board, tag_size=TAG_SIZE, free=AT_CAMCAL_ALL, init=None, max_hamming=0):
+        L = load_library()
+        cfg = AtCamcalConfig(width=int(width), height=int(height), free_mask=int(free), guess=int(init is None))
+        if init is not None:
+            if len(init) == 2:
+                cm, dc = init
+                init = (cm.fx, cm.fy, cm.cx, cm.cy, dc.k1, dc.k2, dc.p1, dc.p2, dc.k3)
+            vals = [float(x) for x in init]
+            if len(vals) != 9:
+                raise ValueError("init holds fx, fy, cx, cy, k1, k2, p1, p2, k3")
+            cfg.init = AtCamera(*vals)
+        tarr, nt = _field_tags(board)
+        h = C.c_void_p()
+        self._h = None
+        rc = L.at_camcal_create(C.byref(cfg), tarr, nt, int(max_hamming), float(tag_size), C.byref(h))
+        if rc < 0:
+            raise FieldPoseError("at_camcal_create", rc)
+        self._h = h
+
+    def add(self, dets):
+        """at_camcal_add: one frame's detections.  True if a board tag was stored, False if the frame
+        had none.  FieldPoseError (AT_E_CAPACITY) beyond AT_CAMCAL_MAX_VIEWS."""
+        arr, n = _detection_records(dets)
+        rc = load_library().at_camcal_add(self._h, arr, n)
+        if rc < 0:
+            raise FieldPoseError("at_camcal_add", rc)
+        return bool(rc)
+
+    def __len__(self):
+        return int(load_library().at_camcal_count(self._h))
+
+    def clear(self):
+        _check(load_library().at_camcal_clear(self._h), "at_camcal_clear")
+
+    def _solve(self, name):
+        out = AtCamcalResult()
+        rc = getattr(load_library(), name)(self._h, C.byref(out))
+        if rc < 0:
+            raise FieldPoseError(name, rc)
+        self.record = out
+        return CameraCalibration(params=np.array([getattr(out.cam, k) for k in CAMCAL_PARAMS]),
+                                 cov=np.array(list(out.cov)).reshape(9, 9), cov_valid=bool(out.cov_valid),
+                                 rms_before=out.rms_before, rms_after=out.rms_after, views_used=out.views_used,
+                                 views_skipped=out.views_skipped, corners=out.corners, accepted=out.accepted,
+                                 rejected=out.rejected)
+
+    def solve(self):
+        """at_camcal_solve: the solve on the GPU (the current device), on the calibrator's own stream."""
+        return self._solve("at_camcal_solve")
+
+    def solve_host(self):
+        """at_camcal_solve_host: the same solve on the CPU, bit-equal records."""
+        return self._solve("at_camcal_solve_host")
+
+    def views(self):
+        """at_camcal_views: one CameraCalView per stored view of the last solve."""
+        L = load_library()
+        n = _check(L.at_camcal_views(self._h, None, 0), "at_camcal_views")
+        buf = (AtCamcalView * max(1, n))()
+        n = _check(L.at_camcal_views(self._h, buf, n), "at_camcal_views")
+        return [CameraCalView(R=np.array(list(b.R)).reshape(3, 3), t=np.array(list(b.t)), rms_px=b.rms_px,
+                              n_tags=b.n_tags, used=bool(b.used)) for b in buf[:n]]
+
+    def set_profiling(self, on=True):
+        _check(load_library().at_camcal_set_profiling(self._h, int(bool(on))), "at_camcal_set_profiling")
+
+    def stats(self):
+        """at_camcal_stats of the last solve."""
+        buf = (C.c_uint64 * 5)()
+        n = _check(load_library().at_camcal_stats(self._h, buf, len(buf)), "at_camcal_stats")
+        names = ("views_used", "views_skipped", "accepted_steps", "rejected_steps", "kernel_ns")
+        return {k: int(v) for k, v in zip(names[:n], buf)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().at_camcal_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -140,6 +140,68 @@ def load_field_layout(layout):
             for tid, R, t in layout]
 
 
+def save_camera_calibration(calibration_dir, serial, cam, dist, rms, extra=None):
+    """Write calibrationmatrix_<serial>.json as the reference's calibration nodes do and
+    load_camera_calibration reads it: "matrix" 3 x 3, "disto" one row of (k1, k2, p1, p2, k3),
+    "rmse_reprojection_error", and "method": "apriltag_board"; `extra` (a dict) adds further keys.
+    Returns the path."""
+    path = os.path.join(calibration_dir, "calibrationmatrix_%s.json" % serial)
+    data = {"matrix": [[float(cam.fx), 0.0, float(cam.cx)], [0.0, float(cam.fy), float(cam.cy)], [0.0, 0.0, 1.0]],
+            "disto": [[float(dist.k1), float(dist.k2), float(dist.p1), float(dist.p2), float(dist.k3)]],
+            "rmse_reprojection_error": float(rms), "method": "apriltag_board"}
+    data.update(extra or {})
+    with open(path, "w") as f:
+        json.dump(data, f, indent=2)
+        f.write("\n")
+    return path
+
+
+def grid_board(rows, cols, first_id, tag_size, pitch):
+    """The layout of a printed grid of tags as CameraCalibrator's `board`: ids first_id,
+    first_id + 1, ... row by row, every tag upright (R = I), the centre of the tag in row r and
+    column c at (c pitch, r pitch, 0) -- x to the right and y down on the sheet, as a tag's own
+    frame, the origin at the centre of the first tag.  pitch is centre to centre and must leave the
+    tags apart (pitch > tag_size)."""
+    if rows < 1 or cols < 1 or first_id < 0 or not tag_size > 0 or not pitch > tag_size:
+        raise ValueError("grid_board: rows, cols >= 1, first_id >= 0, pitch > tag_size > 0")
+    return [(int(first_id) + r * cols + c, np.eye(3), np.array([c * float(pitch), r * float(pitch), 0.0]))
+            for r in range(rows) for c in range(cols)]
+
+
+class CameraCalibrationCollector:
+    """The reference calibration nodes' rule for taking views: a frame with a board tag counts;
+    after `every` such frames in a row the current one goes to the calibrator and the count starts
+    again; a frame without a board tag resets the count; `done` once max_frames views are stored."""
+
+    def __init__(self, calibrator, every=10, max_frames=30):
+        if every < 1 or max_frames < 1:
+            raise ValueError("every, max_frames >= 1")
+        self.calibrator, self.every, self.max_frames = calibrator, int(every), int(max_frames)
+        self.run = 0
+        self.board_ids = None
+
+    @property
+    def done(self):
+        return len(self.calibrator) >= self.max_frames
+
+    def offer(self, dets, board_ids=None):
+        """One frame's detections.  True if the frame was stored as a view.  board_ids (a set of
+        the board's ids) lets a frame count without asking the calibrator; without it every
+        detection counts and the calibrator's own answer decides."""
+        if self.done:
+            return False
+        ids = board_ids if board_ids is not None else self.board_ids
+        seen = any(ids is None or d.id in ids for d in dets)
+        if not seen:
+            self.run = 0
+            return False
+        self.run += 1
+        if self.run < self.every:
+            return False
+        self.run = 0
+        return bool(self.calibrator.add(dets))
+
+
 def draw_detection_outlines(bgr, dets):
     """Outline every tag on a BGR image in place: p0-p1 green, p0-p3 red, p1-p2 and p2-p3
     blue, 2 px (apriltag_utils.cu:54-79; the id text is not drawn)."""
