@@ -584,7 +584,7 @@ int at_create(const at_config* cfg, const at_camera* cam, at_detector** out) {
   b.dets = (DevDetection*)dalloc(B * kMaxDets * sizeof(DevDetection));
   b.det_work = (uint32_t*)dalloc(B * kMaxDets * 4);
   b.quads = (QuadRecord*)dalloc(B * kMaxPairs * sizeof(QuadRecord));
-  b.qpend = (QuadPend*)dalloc(B * kMaxPairs * sizeof(QuadPend));
+  b.fpend = (FitPend*)dalloc(B * kMaxPairs * sizeof(FitPend));
   // control block: per-frame words, scalars, then (8-byte aligned) the timed
   // kernel's two wall-clock stamps and its finished-workgroup count
   d->kstamp_word = (kCtlPerFrame * B + kCtlScalars + 1) & ~(size_t)1;

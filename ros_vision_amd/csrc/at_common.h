@@ -258,17 +258,21 @@ struct Moments {
   int32_t N;
 };
 
-// A kept blob's side fits left to k_quad_fin (throughput mode): per side segment of its
-// best combination, FitLine's (float)(Cxx - Cyy), (float)(2 Cxy) and centroid quotients
-// (all the corners need of the fit), and the record's fields.  The blob's team writes
-// them (threads 0-3 a segment each); k_quad_fin finishes the four lines, the corners
-// and the Heron / angle tests.
-struct QuadPend {
-  float fit[4][4];
-  uint32_t blob_index, valid;
-  uint16_t indices[4];
+// A kept blob handed from the (non-FUSE) blob kernels to k_fit_quads, which runs FitQuads
+// from the segment fits on: the blob's point count, its peak count, the top peaks' point
+// indices in ascending order (pad 0xffff) and the inclusive prefix moments FitQuads reads,
+// in BlobShared's order: [k] = P[pi[k]], [10 + k] = P[pi[k] - 1], [20] = P[n - 1] (the
+// entries no segment of the blob reads are not written).  The blob's team writes the whole
+// record of every blob it selects; k_fit_quads copies it into LDS by 16-byte words.
+struct alignas(16) FitPend {
+  uint32_t n, cnt, blob_index;
+  uint16_t pi[kNMaxima];
+  uint32_t tMx[21], tMy[21], tW[21];
+  uint32_t pad0;
+  uint64_t tMxx[21], tMyy[21], tMxy[21];
+  uint64_t pad1;
 };
-static_assert(sizeof(QuadPend) == 80, "QuadPend: 80 B per kept blob");
+static_assert(sizeof(FitPend) == 800, "FitPend: 800 B per kept blob");
 
 // (DrawPrim, one 2-px-thick segment of the annotated image: at_preview.h)
 
@@ -366,7 +370,7 @@ struct DevBufs {
   uint32_t* ctrl;       // device control block base
   uint32_t ctrl_words;
   QuadRecord* quads;  // [B][kMaxPairs]  fitted-quad debug record of each kept blob, slot = pair rank
-  QuadPend* qpend;    // [B][kMaxPairs]  side-fit inputs of each kept blob (throughput mode), slot = pair rank
+  FitPend* fpend;     // [B][kMaxPairs]  hand-over record of each kept blob (non-FUSE blob kernels -> k_fit_quads), slot = pair rank
   // control block (zeroed every batch)
   uint32_t* npts;     // [B]
   uint32_t* npairs;   // [B]

@@ -103,6 +103,12 @@ __device__ __forceinline__ uint32_t wave_read_next(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, false);
 }
 
+// a value that every lane of the wave holds, moved into a scalar register: what is
+// computed from it (bases, trip counts, branches) is scalar too
+__device__ __forceinline__ uint32_t wave_uniform(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
 // value of lane `l` in every lane (scalar read)
 template <typename T>
 __device__ __forceinline__ T wave_read(T v, int l) {
@@ -2514,7 +2520,7 @@ __device__ __forceinline__ void line_normal(float d, float c, float h, double* l
 
 // FitLine (line_fit_filter.cu:798-872) / HostFitLine (apriltag_detect.cu:38-90).
 // pre (optional): d, c and the centroid quotients, which are all UpdateFitQuads'
-// corners need of the fit (k_quad_fin finishes from them)
+// corners need of the fit (k_fit_quads finishes the side lines from them)
 __device__ void fit_line(const Moments& m, double* lp01, double* lp23, double* err, double* mse, float* pre = nullptr) {
   const int64_t W = m.W;
   const int64_t Cxx = (int64_t)((uint64_t)m.Mxx * (uint64_t)W - (uint64_t)((int64_t)m.Mx * (int64_t)m.Mx));
@@ -2950,7 +2956,72 @@ struct SegFits {
   double err[kNMaxima][kNMaxima];
   double mse[kNMaxima][kNMaxima];
   double p[kNMaxima][kNMaxima][2];
+  __device__ __forceinline__ void put(int a, int bb, const LineFitOut& o) {
+    err[a][bb] = o.err; mse[a][bb] = o.mse; p[a][bb][0] = o.p23[0]; p[a][bb][1] = o.p23[1];
+  }
+  __device__ __forceinline__ double e(int a, int bb) const { return err[a][bb]; }
+  __device__ __forceinline__ double m(int a, int bb) const { return mse[a][bb]; }
+  __device__ __forceinline__ double nx(int a, int bb) const { return p[a][bb][0]; }
+  __device__ __forceinline__ double ny(int a, int bb) const { return p[a][bb][1]; }
 };
+// The same fits as k_fit_quads keeps them, one 16-byte word per segment: FitLine's err,
+// mse and normal are floats widened to double (fit_line), so the float holds each exactly.
+struct SegFitsF {
+  float4 v[kNMaxima][kNMaxima];  // err, mse, nx, ny
+  __device__ __forceinline__ void put(int a, int bb, const LineFitOut& o) {
+    v[a][bb] = make_float4((float)o.err, (float)o.mse, (float)o.p23[0], (float)o.p23[1]);
+  }
+  __device__ __forceinline__ double e(int a, int bb) const { return (double)v[a][bb].x; }
+  __device__ __forceinline__ double m(int a, int bb) const { return (double)v[a][bb].y; }
+  __device__ __forceinline__ double nx(int a, int bb) const { return (double)v[a][bb].z; }
+  __device__ __forceinline__ double ny(int a, int bb) const { return (double)v[a][bb].w; }
+};
+
+// read_moments (line_fit_filter.cu:745-796) of the segment pi[a] -> pi[b] of a blob of n
+// points, from the prefix moments P of BlobShared or FitPend (same member names)
+template <typename P>
+__device__ __forceinline__ Moments seg_moments(const P& S, uint32_t n, int a, int bb) {
+  const uint32_t i0 = (uint32_t)S.pi[a], i1 = (uint32_t)S.pi[bb];
+  Mom6 m = Mom6{S.tMx[bb], S.tMy[bb], S.tW[bb], S.tMxx[bb], S.tMyy[bb], S.tMxy[bb]};
+  const Mom6 pm = Mom6{S.tMx[10 + a], S.tMy[10 + a], S.tW[10 + a], S.tMxx[10 + a], S.tMyy[10 + a], S.tMxy[10 + a]};
+  int32_t N;
+  if (i0 < i1) {
+    if (i0 > 0) mom_sub(m, pm);
+    N = (int32_t)(i1 - i0 + 1);
+  } else {
+    Mom6 z = Mom6{S.tMx[20], S.tMy[20], S.tW[20], S.tMxx[20], S.tMyy[20], S.tMxy[20]};
+    mom_sub(z, pm);
+    mom_add(z, m);
+    m = z;
+    N = (int32_t)(n - i0 + i1 + 1);
+  }
+  return to_moments(m, N);
+}
+
+// QuadFitCalculator's test of one combination cb = m0 | m1 << 8 | m2 << 16 | m3 << 24 of
+// peaks: the four sides' summed fit error, DBL_MAX when a side's mse or the first corner's
+// cosine is over the limit
+template <typename SF>
+__device__ __forceinline__ double combo_err(const SF& seg, uint32_t cb, double mse_max, double cos_critical) {
+  const int m0 = cb & 0xff, m1 = (cb >> 8) & 0xff, m2 = (cb >> 16) & 0xff, m3 = cb >> 24;
+  double e4 = DBL_MAX;
+  if (!(seg.m(m0, m1) > mse_max)) {
+    if (!(seg.m(m1, m2) > mse_max)) {
+      const double dot = seg.nx(m0, m1) * seg.nx(m1, m2) + seg.ny(m0, m1) * seg.ny(m1, m2);
+      if (!(fabs(dot) > cos_critical)) {
+        if (!(seg.m(m2, m3) > mse_max) && !(seg.m(m3, m0) > mse_max))
+          e4 = seg.e(m0, m1) + seg.e(m1, m2) + seg.e(m2, m3) + seg.e(m3, m0);
+      }
+    }
+  }
+  return e4;
+}
+
+// combinations FitQuads tests for a blob of cnt peaks: C(min(cnt, 10), 4), the first in
+// colexicographic order
+__device__ __forceinline__ int num_combos(int cnt) {
+  return cnt < 4 ? 0 : cnt >= kNMaxima ? 210 : (cnt * (cnt - 1) * (cnt - 2) * (cnt - 3)) / 24;
+}
 
 template <int NT, int CAP>
 struct BlobShared {
@@ -3912,6 +3983,30 @@ __device__ void blob_item(const DevBufs& b, const Geom& g, const Params& prm, Bl
     else if (k < 20) { need = k - 10 < cnt && k - 10 < kNMaxima && S.pi[k - 10] > 0; idx = need ? (uint32_t)S.pi[k - 10] - 1 : 0; }
     else if (k == 20) { need = true; idx = n - 1; }
     const Mom6 p = prefix_at<NT, CAP>(S, cw, cbase, c, idx, need);
+    if constexpr (!FUSE) {
+      // FitQuads from here on runs in k_fit_quads, a row of 16 lanes per blob: this team
+      // leaves it the blob's hand-over record.  k_fit_quads reads the record of every work
+      // item whose pair_sel is set and relies on this batch having written it: between the
+      // pair_sel test above and these stores there is no return but the diagnostic cuts
+      // (AT_DIAG_BLOB_STOP 2-4), under which k_fit_quads is not launched.  Whoever adds an
+      // early exit there must write the record first (cnt = 0 makes an invalid quad).
+      FitPend& fp = b.fpend[(size_t)f * kMaxPairs + rank];
+      if (need) {
+        fp.tMx[k] = p.Mx; fp.tMy[k] = p.My; fp.tW[k] = p.W;
+        fp.tMxx[k] = p.Mxx; fp.tMyy[k] = p.Myy; fp.tMxy[k] = p.Mxy;
+      }
+      if (k < kNMaxima) fp.pi[k] = (uint16_t)S.pi[k];
+      if (tid == 0) {
+        fp.n = n;
+        fp.cnt = npk;
+        fp.blob_index = bi;
+        pacc[21] += 1;  // FitQuads records of this team (batch statistics)
+      }
+      phase(6);
+      phase(9);
+      team_sync<NT>();  // (S.pi and the prefix state are read until here; the next item rewrites them)
+      return;
+    }
     if (need) {
       S.tMx[k] = p.Mx; S.tMy[k] = p.My; S.tW[k] = p.W;
       S.tMxx[k] = p.Mxx; S.tMyy[k] = p.Myy; S.tMxy[k] = p.Mxy;
@@ -3919,24 +4014,6 @@ __device__ void blob_item(const DevBufs& b, const Geom& g, const Params& prm, Bl
   }
   team_sync<NT>();
   phase(6);
-  // read_moments (line_fit_filter.cu:745-796) of the segment pi[a] -> pi[b]
-  auto seg_moments = [&](int a, int bb) -> Moments {
-    const uint32_t i0 = (uint32_t)S.pi[a], i1 = (uint32_t)S.pi[bb];
-    Mom6 m = Mom6{S.tMx[bb], S.tMy[bb], S.tW[bb], S.tMxx[bb], S.tMyy[bb], S.tMxy[bb]};
-    const Mom6 pm = Mom6{S.tMx[10 + a], S.tMy[10 + a], S.tW[10 + a], S.tMxx[10 + a], S.tMyy[10 + a], S.tMxy[10 + a]};
-    int32_t N;
-    if (i0 < i1) {
-      if (i0 > 0) mom_sub(m, pm);
-      N = (int32_t)(i1 - i0 + 1);
-    } else {
-      Mom6 z = Mom6{S.tMx[20], S.tMy[20], S.tW[20], S.tMxx[20], S.tMyy[20], S.tMxy[20]};
-      mom_sub(z, pm);
-      mom_add(z, m);
-      m = z;
-      N = (int32_t)(n - i0 + i1 + 1);
-    }
-    return to_moments(m, N);
-  };
   // every segment a combination can use, fitted once (FitLine on the same
   // moments as QuadFitCalculator's per-combination fits: identical results),
   // over the key area (its compact words were last read by the prefix lookups)
@@ -3949,11 +4026,7 @@ __device__ void blob_item(const DevBufs& b, const Geom& g, const Params& prm, Bl
   for (int ci = tid; cnt >= 4 && ci < cn * cn; ci += NT) {
     const int a = (int)(((float)ci + 0.5f) * rcn), bb = ci - a * cn;  // (exact: ci + 0.5 is >= 0.05 from a multiple of cn)
     if (a != bb) {
-      const LineFitOut o = fit_line_v<false, true>(seg_moments(a, bb));
-      seg.err[a][bb] = o.err;
-      seg.mse[a][bb] = o.mse;
-      seg.p[a][bb][0] = o.p23[0];
-      seg.p[a][bb][1] = o.p23[1];
+      seg.put(a, bb, fit_line_v<false, true>(seg_moments(S, n, a, bb)));
     }
   }
   team_sync<NT>();
@@ -3964,24 +4037,11 @@ __device__ void blob_item(const DevBufs& b, const Geom& g, const Params& prm, Bl
   double err = DBL_MAX;
   uint32_t bt = 0xffffffffu;
   const double mse_max = (double)prm.max_line_fit_mse;
-  const int ncomb = cnt < 4 ? 0 : cnt >= kNMaxima ? 210 : (cnt * (cnt - 1) * (cnt - 2) * (cnt - 3)) / 24;
+  const int ncomb = num_combos(cnt);
   for (int cj = tid; cj < ncomb; cj += NT) {
-    double e4 = DBL_MAX;
     const int ci = (int)combo[210 + cj];
-    {
-      const uint32_t cb = combo[ci];  // LDS copy of c_combo: no vector-memory wait in this loop
-      const int m0 = cb & 0xff, m1 = (cb >> 8) & 0xff, m2 = (cb >> 16) & 0xff, m3 = cb >> 24;
-      if (!(seg.mse[m0][m1] > mse_max)) {
-        if (!(seg.mse[m1][m2] > mse_max)) {
-          const double dot =
-              seg.p[m0][m1][0] * seg.p[m1][m2][0] + seg.p[m0][m1][1] * seg.p[m1][m2][1];
-          if (!(fabs(dot) > prm.cos_critical_rad)) {
-            if (!(seg.mse[m2][m3] > mse_max) && !(seg.mse[m3][m0] > mse_max))
-              e4 = seg.err[m0][m1] + seg.err[m1][m2] + seg.err[m2][m3] + seg.err[m3][m0];
-          }
-        }
-      }
-    }
+    // (combo: the LDS copy of c_combo, no vector-memory wait in this loop)
+    const double e4 = combo_err(seg, combo[ci], mse_max, prm.cos_critical_rad);
     if (bt == 0xffffffffu || e4 < err || (e4 == err && (uint32_t)ci < bt)) { err = e4; bt = (uint32_t)ci; }
   }
   // BlockReduce(MinQuadError): minimum error, first (lowest) combination on ties
@@ -4007,31 +4067,10 @@ __device__ void blob_item(const DevBufs& b, const Geom& g, const Params& prm, Bl
   uint16_t qidx[4];
   const uint32_t cbt = combo[bt];
   for (int k = 0; k < 4; k++) qidx[k] = (uint16_t)S.pi[(cbt >> (8 * k)) & 0xff];
-  if constexpr (!FUSE) {
-    // throughput mode: the side segments' moments for k_quad_fin (a thread per blob
-    // there, instead of a few lanes of this team on a serial fp64 chain here)
-    QuadPend& qp = b.qpend[(size_t)f * kMaxPairs + rank];
-    if (valid && tid < 4) {
-      float pre[4];
-      double e_, m_;
-      fit_line(seg_moments((cbt >> (8 * tid)) & 0xff, (cbt >> (8 * ((tid + 1) & 3))) & 0xff), nullptr, nullptr, &e_, &m_,
-               pre);
-      *reinterpret_cast<float4*>(qp.fit[tid]) = make_float4(pre[0], pre[1], pre[2], pre[3]);
-    }
-    if (tid == 0) {
-      qp.blob_index = bi;
-      qp.valid = valid;
-      for (int k = 0; k < 4; k++) qp.indices[k] = qidx[k];
-      pacc[21] += 1;  // FitQuads records of this team (batch statistics)
-    }
-    phase(9);
-    team_sync<NT>();
-    return;
-  }
   // UpdateFitQuads (apriltag_detect.cu:98-241): side lines in parallel, rest on one lane
   if (valid && tid < 4) {
     const LineFitOut o =
-        fit_line_v<true, true>(seg_moments((cbt >> (8 * tid)) & 0xff, (cbt >> (8 * ((tid + 1) & 3))) & 0xff));
+        fit_line_v<true, true>(seg_moments(S, n, (cbt >> (8 * tid)) & 0xff, (cbt >> (8 * ((tid + 1) & 3))) & 0xff));
     S.lines[tid][0] = o.p01[0];
     S.lines[tid][1] = o.p01[1];
     S.lines[tid][2] = o.p23[0];
@@ -4170,13 +4209,16 @@ __device__ __forceinline__ bool work_item(const DevBufs& b, const uint32_t* cnt,
 
 // One candidate with a team of NT threads (a wave, or the whole workgroup for
 // large candidates); red: NT/64 x 8 LDS words for the cross-wave reduction.
+// (w, n, off: the work word and the pair's count and offset, which the wave-per-candidate
+// caller holds in scalar registers: the bases below are then scalar and every load and
+// store takes a 32-bit lane offset)
 template <int NT>
-__device__ __forceinline__ void extents_item(const DevBufs& b, const Geom& g, uint32_t w, int64_t (*red)[8]) {
-  const int tid = team_rank<NT>();
+__device__ __forceinline__ void extents_item(const DevBufs& b, const Geom& g, uint32_t w, uint32_t n, uint32_t off,
+                                             int64_t (*red)[8]) {
+  const uint32_t tid = (uint32_t)team_rank<NT>();
   const int f = (int)(w >> 16);
   const uint32_t rank = w & 0xffff;
-  const uint32_t n = b.pair_cnt[(size_t)f * kMaxPairs + rank];
-  const size_t so = (size_t)f * g.cap_pts + b.pair_off[(size_t)f * kMaxPairs + rank];
+  const size_t so = (size_t)f * g.cap_pts + off;
   const uint32_t* grp = b.grp + so;
   uint64_t* keys = b.keys + so;
   const uint8_t* dec = b.dec + (size_t)f * g.Wd * g.Hd;
@@ -4248,9 +4290,11 @@ __device__ __forceinline__ void extents_item(const DevBufs& b, const Geom& g, ui
   if (!keep) return;  // uniform across the team
   if (tid == 0) b.pair_sel[(size_t)f * kMaxPairs + rank] = 1;
   const double cx = ext_cx(e), cy = ext_cy(e);
+  const uint32_t Wd = (uint32_t)g.Wd;
   for (uint32_t base = 0; base < n; base += NT * U) {
     uint32_t kk[U];
     uint32_t gp[U];
+    uint32_t pxy[U];  // a point unpacked once for the loads and the keys: px | py << 12 | (gradient pixel in the image) << 31
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const uint32_t t = base + u * NT + tid;
@@ -4258,42 +4302,46 @@ __device__ __forceinline__ void extents_item(const DevBufs& b, const Geom& g, ui
     }
     // line-fit weight of TransformLineFitPoint (apriltag_gpu.cu:631-687): gradient
     // of the decimated image at ((px + 1) / 2, (py + 1) / 2); the four bytes of
-    // every point of the round are loaded first (out-of-range: a fixed pixel)
+    // every point of the round are loaded first (out-of-range: a fixed pixel), the
+    // horizontal neighbours from one address
 #pragma unroll
     for (int u = 0; u < U; u++) {
-      const uint64_t k = kk[u];
+      const uint32_t k = kk[u];
       const int dxy = (int)(k & 3);
-      const int32_t ix = (int32_t)(((k >> 14) & 0x3ff) * 2 + dx_of(dxy) + 1) / 2;
-      const int32_t iy = (int32_t)(((k >> 4) & 0x3ff) * 2 + dy_of(dxy) + 1) / 2;
-      const bool in = base + u * NT + tid < n && ix > 0 && ix + 1 < g.Wd && iy > 0 && iy + 1 < g.Hd;
-      const int32_t at = in ? iy * g.Wd + ix : g.Wd + 1;
-      gp[u] = (uint32_t)dec[at - 1] | ((uint32_t)dec[at + 1] << 8) | ((uint32_t)dec[at - g.Wd] << 16) |
-              ((uint32_t)dec[at + g.Wd] << 24);
+      const uint32_t px = ((k >> 14) & 0x3ff) * 2 + dx_of(dxy), py = ((k >> 4) & 0x3ff) * 2 + dy_of(dxy);
+      // (grouped points belong to interior pixels, bx, by >= 1: px, py lie in [1, 2047])
+      const uint32_t ix = (px + 1) / 2, iy = (py + 1) / 2;
+      const bool img = ix > 0 && ix + 1 < Wd && iy > 0 && iy + 1 < (uint32_t)g.Hd;
+      const bool in = base + u * NT + tid < n && img;
+      pxy[u] = (px & 0xfff) | ((py & 0xfff) << 12) | ((uint32_t)img << 31);
+      const uint32_t at = in ? iy * Wd + ix : Wd + 1;
+      const uint8_t* hp = dec + (at - 1);
+      gp[u] = (uint32_t)hp[0] | ((uint32_t)hp[2] << 8) | ((uint32_t)dec[at - Wd] << 16) | ((uint32_t)dec[at + Wd] << 24);
     }
 #pragma unroll AT_EXT_KEY_UNROLL
     for (int u = 0; u < U; u++) {
       const uint32_t t = base + u * NT + tid;
       if (t >= n) continue;
-      const uint64_t k = kk[u];
-      const int dxy = (int)(k & 3);
+      const uint32_t k = kk[u];
+      const uint32_t dxy = k & 3;
       const uint32_t bx = (k >> 14) & 0x3ff, by = (k >> 4) & 0x3ff;
-      const uint32_t px = bx * 2 + dx_of(dxy), py = by * 2 + dy_of(dxy);
+      const uint32_t px = pxy[u] & 0xfff, py = (pxy[u] >> 12) & 0xfff;
       const float dyf = (float)((double)py - cy);
       const float dxf = (float)((double)px - cx);
       const float theta = (float)(((double)det_atan2f(dyf, dxf) + 3.14159265358979323846) * 8e6);
-      long long ti = (long long)rintf(theta);
-      if (ti < 0) ti = 0;
-      const int32_t ix = (int32_t)(px + 1) / 2, iy = (int32_t)(py + 1) / 2;
+      // atan2f lies in [-pi_f, pi_f] and pi_f - pi < 1e-7, so -0.7 < theta < 5.03e7 < 2^31: a
+      // 32-bit conversion is exact, and the one value below 0 it can give (-1) is clamped
+      const uint32_t ti = (uint32_t)max((int32_t)rintf(theta), 0);
       int32_t Wt = 1;
-      if (ix > 0 && ix + 1 < g.Wd && iy > 0 && iy + 1 < g.Hd) {
+      if (pxy[u] >> 31) {
         const int32_t gxv = (int32_t)((gp[u] >> 8) & 0xff) - (int32_t)(gp[u] & 0xff);
         const int32_t gyv = (int32_t)(gp[u] >> 24) - (int32_t)((gp[u] >> 16) & 0xff);
         Wt = lf_weight(gxv, gyv);
       }
       // sort key: order (theta, plane, y, x) == P6 stable order; b2w and W ride in
       // the low bits (never decide: (plane, y, x) is unique)
-      keys[t] = ((uint64_t)(ti & 0xfffffff) << kKeyTheta) | ((uint64_t)dxy << 30) | ((uint64_t)by << 20) |
-               ((uint64_t)bx << 10) | (((k >> 3) & 1) << 9) | (uint64_t)Wt;
+      const uint32_t lo = (dxy << 30) | (by << 20) | (bx << 10) | (((k >> 3) & 1) << 9) | (uint32_t)Wt;
+      keys[t] = ((uint64_t)(ti & 0xfffffff) << kKeyTheta) | lo;
     }
   }
 }
@@ -4325,14 +4373,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(AT_EXT_WAVE
   for (uint32_t it = blockIdx.x; it < nlarge; it += gridDim.x) {
     uint32_t w = 0;
     work_item(b, cnt, 0, kNumCls, it, &w);
-    extents_item<256>(b, g, w, s_red);
+    const size_t pr = (size_t)(w >> 16) * kMaxPairs + (w & 0xffff);
+    extents_item<256>(b, g, w, b.pair_cnt[pr], b.pair_off[pr], s_red);
   }
   if (g.ctw != 32) {  // latency mode: k_blob_small<true> does the small candidates itself
-    const uint32_t gw = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
+    // the wave's index, its work word and the pair's count and offset are the same in
+    // every lane: scalar registers
+    const uint32_t gw = blockIdx.x * 4 + wave_uniform(threadIdx.x >> 6), nw = gridDim.x * 4;
     for (uint32_t it = nlarge + gw; it < total; it += nw) {
       uint32_t w = 0;
       work_item(b, cnt, 0, kNumCls, it, &w);
-      extents_item<64>(b, g, w, nullptr);
+      w = wave_uniform(w);
+      const size_t pr = (size_t)(w >> 16) * kMaxPairs + (w & 0xffff);
+      extents_item<64>(b, g, w, wave_uniform(b.pair_cnt[pr]), wave_uniform(b.pair_off[pr]), nullptr);
     }
   }
   __syncthreads();
@@ -4414,19 +4467,27 @@ __device__ __forceinline__ void small_blob_loop(const DevBufs& b, const Geom& g,
   if (lane == 0) S.slow_dt = 0;
   uint32_t nwork = 0;
   for (int c = c0; c < c1; c++) nwork += s_cnt[c];
-  uint32_t item = wv;
+  // throughput mode: the item's state -- wave index, work word, the pair's count, offset
+  // and selection -- is the same in every lane; held in scalar registers, the blob's
+  // bases, trip counts and branches on them are scalar too
+  auto uni = [](uint32_t v) { return FUSE ? v : wave_uniform(v); };
+  auto uni_pair = [&](const PairInfo& p) { return PairInfo{uni(p.n), uni(p.off), uni(p.sel)}; };
+  uint32_t item = uni(wv);
   uint32_t w = 0, w1 = 0;
   PairInfo pi = {0, 0, 0};
   if (item < nwork) {
     work_item(b, s_cnt, c0, c1, item, &w);
-    pi = load_pair_info(b, w);
+    w = uni(w);
+    pi = uni_pair(load_pair_info(b, w));
   }
   if (item + nwaves < nwork) work_item(b, s_cnt, c0, c1, item + nwaves, &w1);
   for (; item < nwork; item += nwaves) {
     const bool has1 = item + nwaves < nwork;
+    w1 = uni(w1);
     const PairInfo pi1 = has1 ? load_pair_info(b, w1) : PairInfo{0, 0, 0};
     uint32_t w2 = 0;
     if (item + 2 * nwaves < nwork) work_item(b, s_cnt, c0, c1, item + 2 * nwaves, &w2);
+    pi = uni_pair(pi);
     [[clang::always_inline]] blob_item<64, CAP, FUSE>(b, g, prm, S, nullptr, s_combo, w, pi, pacc);
     w = w1;
     pi = pi1;
@@ -4492,7 +4553,7 @@ template <bool FUSE, int CAP = kSmallBlob, int WAVES = AT_BS_WAVES, int STAGE = 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FUSE ? 2 : WAVES))) void k_blob_small(DevBufs b, Geom g, Params prm,
                                                                                                          int c0, int c1, int launch) {
   __shared__ BlobShared<64, CAP> Ss[4];
-  const int wave = threadIdx.x >> 6;
+  const int wave = FUSE ? (int)(threadIdx.x >> 6) : (int)wave_uniform(threadIdx.x >> 6);
   uint32_t kt_slot = ~0u;
   if (!launch) {
     kt_begin(b, STAGE);
@@ -4542,121 +4603,229 @@ __global__ __launch_bounds__(512) void k_blob_lat(DevBufs b, Geom g, Params prm)
   }
 }
 
-// Throughput mode's end of FitQuads (UpdateFitQuads, apriltag_detect.cu:98-241) for the
-// kept blobs of size classes c0 .. c1-1, four lanes (a DPP quad) per blob: lane k fits
-// side line k from the moments the blob kernels left in QuadPend, intersects it with
-// line k+1 (corner k), measures Heron side k (lanes 0, 1 also sides 4, 5) and tests
-// corner angle k; lane 0 writes the debug record and the accepted quad's decode-queue
-// entry.  The expressions are the team version's in blob_item (which latency mode keeps).
-__global__ __launch_bounds__(256) void k_quad_fin(DevBufs b, Geom g, Params prm, int c0, int c1) {
-  __shared__ uint32_t s_cnt[kNumCls];
+// FitQuads from the segment fits on (K11's QuadFitCalculator and UpdateFitQuads,
+// apriltag_detect.cu:98-241) for the kept blobs of size classes c0 .. c1-1 that the
+// non-FUSE blob kernels handed over (FitPend): a row of 16 lanes per blob, four blobs per
+// wave.  A wave looks at AT_FQ_ITEMS work items, one per lane, and takes the selected
+// ones four at a time.  Per blob: the row copies the record into LDS; the segment fits
+// its combinations can use (73 for 10 peaks) in up to five row rounds; the C(cn, 4) <=
+// 210 combinations in up to 14, in
+// colexicographic order, each lane keeping its minimum and the lowest lexicographic index
+// on ties, then the row's argmin by the same rule (the reference's first minimum); the
+// row's lanes 0-3 then fit side line k, intersect it with line k+1 (corner k), measure
+// Heron side k (lanes 0, 1 also sides 4, 5) and test corner angle k; lane 0 writes the
+// debug record and the accepted quad's decode-queue entry.  The expressions are the
+// team version's in blob_item (which the FUSE kernels keep).
+struct FitRow {
+  FitPend rec;
+  SegFitsF seg;
+};
+// The segments a combination m0 < m1 < m2 < m3 of 10 peaks can use: a side m0 -> m1,
+// m1 -> m2 or m2 -> m3 is a forward segment a < bb (45), the closing side m3 -> m0 a
+// segment a >= bb + 3 that wraps around the end of the point list (28).  Only the sides
+// m0 -> m1 and m1 -> m2 are asked for their normals, so the closing segments' fits
+// leave them out.
+constexpr int kFitFwd = kNMaxima * (kNMaxima - 1) / 2, kFitCls = (kNMaxima - 3) * (kNMaxima - 2) / 2;
+// work items a wave looks at per sweep, one per lane of its first rows (about two thirds
+// are selected: five or six groups of four).  8, 16, 32 and 64 per sweep: the serialized
+// kernel is shortest at 8 (64 leave most of the grid without work), the concurrent
+// throughput highest at 32 (profiles/fit_rows/items_ab_stages.txt).
+#ifndef AT_FQ_ITEMS
+#define AT_FQ_ITEMS 32
+#endif
+__global__ __launch_bounds__(256) void k_fit_quads(DevBufs b, Geom g, Params prm, int c0, int c1) {
+  __shared__ FitRow s_row[16];
+  __shared__ uint32_t s_combo[420], s_cnt[kNumCls];
+  __shared__ uint16_t s_pair[kFitFwd + kFitCls];
+  load_combos(s_combo, threadIdx.x, 256);
+  if (threadIdx.x < kFitFwd) {  // forward segments a < bb, by bb: the first cn (cn - 1) / 2 are those of cn peaks
+    int bb = 1;
+    while (bb * (bb + 1) / 2 <= (int)threadIdx.x) bb++;
+    s_pair[threadIdx.x] = (uint16_t)((threadIdx.x - bb * (bb - 1) / 2) | (bb << 8));
+  } else if (threadIdx.x < kFitFwd + kFitCls) {  // closing segments a >= bb + 3, by a: the first (cn - 3) (cn - 2) / 2
+    const int u = (int)threadIdx.x - kFitFwd;
+    int a = 3;
+    while ((a - 2) * (a - 1) / 2 <= u) a++;
+    s_pair[threadIdx.x] = (uint16_t)(a | ((u - (a - 3) * (a - 2) / 2) << 8));
+  }
   if (threadIdx.x < kNumCls) s_cnt[threadIdx.x] = min(b.ncls[threadIdx.x], b.wcap);
   __syncthreads();
   uint32_t nwork = 0;
   for (int c = c0; c < c1; c++) nwork += s_cnt[c];
-  const uint32_t lane = lane_id(), base = lane & ~3u;
-  const int k = (int)(lane & 3);
+  const uint32_t lane = lane_id(), base = lane & ~15u;
+  const int rl = (int)(lane & 15), row = (int)(lane >> 4);
+  const int k = rl & 3;
+  const uint32_t wv = wave_uniform(blockIdx.x * 4 + (threadIdx.x >> 6));
+  FitRow& R = s_row[threadIdx.x >> 4];
+  const double mse_max = (double)prm.max_line_fit_mse;
   auto from = [&](double v, int j) { return __shfl(v, (int)base + j); };
   auto fromf = [&](float v, int j) { return __shfl(v, (int)base + j); };
   auto quad_or = [&](int v) {
     v |= __shfl_xor(v, 1);
     return v | __shfl_xor(v, 2);
   };
-  // (the four lanes of a quad share the item: every shuffle reads an active lane)
-  for (uint32_t it = (blockIdx.x * 256 + threadIdx.x) >> 2; it < nwork; it += gridDim.x * 64) {
-    uint32_t w = 0;
-    work_item(b, s_cnt, c0, c1, it, &w);
-    const uint32_t f = w >> 16, rank = w & 0xffff;
-    const size_t slot = (size_t)f * kMaxPairs + rank;
-    if (b.pair_sel[slot] == 0) continue;  // (the blob kernels skipped it too)
-    const QuadPend& qp = b.qpend[slot];
-    const bool valid = qp.valid != 0;
-    float cx = 0.f, cy = 0.f;
-    int bad = 0;
-    {
-      double l[4] = {0, 0, 0, 0};
-      if (valid) {  // fit_line's p01 and p23 from the blob team's d, c and centroid
-        const float4 pre = *reinterpret_cast<const float4*>(qp.fit[k]);
-        l[0] = (double)pre.z;
-        l[1] = (double)pre.w;
-        line_normal(pre.x, pre.y, det_hypotf(pre.x, pre.y), l + 2);
-      }
-      double m[4];
+  for (uint32_t it0 = wv * AT_FQ_ITEMS; it0 < nwork; it0 += gridDim.x * 4 * AT_FQ_ITEMS) {
+    uint32_t wl = 0;
+    bool sel = false;
+    if (lane < AT_FQ_ITEMS && it0 + lane < nwork) {
+      work_item(b, s_cnt, c0, c1, it0 + lane, &wl);
+      sel = b.pair_sel[(size_t)(wl >> 16) * kMaxPairs + (wl & 0xffff)] != 0;  // (the blob kernels skipped the others too)
+    }
+    uint64_t todo = __ballot(sel);
+    while (todo) {  // (uniform) row r takes the r-th selected item left
+      int src = -1;
 #pragma unroll
-      for (int j = 0; j < 4; j++) m[j] = from(l[j], (k + 1) & 3);  // line k+1
-      if (valid) {
-        const double A00 = l[3], A01 = -m[3];
-        const double A10 = -l[2], A11 = m[2];
-        const double B0 = -l[0] + m[0];
-        const double B1 = -l[1] + m[1];
-        const double det = A00 * A11 - A10 * A01;
-        const double W00 = A11 / det, W01 = -A01 / det;
-        if (fabs(det) < 0.001) {
-          bad = 1;
-        } else {
-          const double L0 = W00 * B0 + W01 * B1;
-          cx = (float)(l[0] + L0 * A00);
-          cy = (float)(l[1] + L0 * A10);
+      for (int r = 0; r < 4; r++) {
+        if (todo) {
+          if (row == r) src = __builtin_ctzll(todo);
+          todo &= todo - 1;
         }
       }
-    }
-    bool ok = valid && !quad_or(bad);
-    float qc[4][2];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      qc[j][0] = fromf(cx, j);
-      qc[j][1] = fromf(cy, j);
-    }
-    if (ok) {
-      // sides of triangles (0,1,2) and (2,3,0): 0->1, 1->2, 2->0, 2->3, 3->0, 0->2;
-      // lane k side k, lanes 0 and 1 also side 4 + k
-      auto side = [&](int j) {
-        const int a2 = j == 0 ? 0 : j == 1 ? 1 : j == 2 ? 2 : j == 3 ? 2 : j == 4 ? 3 : 0;
-        const int b2 = j == 0 ? 1 : j == 1 ? 2 : j == 2 ? 0 : j == 3 ? 3 : j == 4 ? 0 : 2;
-        return det_hypotf(qc[b2][0] - qc[a2][0], qc[b2][1] - qc[a2][1]);
-      };
-      const float s0 = side(k), s1 = side(4 + (k & 1));
-      float len[6];
-#pragma unroll
-      for (int j = 0; j < 4; j++) len[j] = fromf(s0, j);
-      len[4] = fromf(s1, 0);
-      len[5] = fromf(s1, 1);
-      float area = 0, pp;
-      pp = (len[0] + len[1] + len[2]) / 2;
-      area += sqrtf(pp * (pp - len[0]) * (pp - len[1]) * (pp - len[2]));
-      pp = (len[3] + len[4] + len[5]) / 2;
-      area += sqrtf(pp * (pp - len[3]) * (pp - len[4]) * (pp - len[5]));
-      if ((double)area < 0.95 * g.min_tag_width * g.min_tag_width) ok = false;
-    }
-    if (ok) {
-      const int i0 = k, i1 = (i0 + 1) & 3, i2 = (i0 + 2) & 3;
-      const float dx1 = qc[i1][0] - qc[i0][0], dy1 = qc[i1][1] - qc[i0][1];
-      const float dx2 = qc[i2][0] - qc[i1][0], dy2 = qc[i2][1] - qc[i1][1];
-      const float cosd = (dx1 * dx2 + dy1 * dy2) / sqrtf((dx1 * dx1 + dy1 * dy1) * (dx2 * dx2 + dy2 * dy2));
-      const int abad = (double)fabsf(cosd) > prm.cos_critical_rad || dx1 * dy2 < dy1 * dx2;
-      if (quad_or(abad)) ok = false;
-    }
-    if (k == 0) {
-      QuadRecord rec;
-      rec.blob_index = qp.blob_index;
-      rec.valid = valid;
-      for (int j = 0; j < 4; j++) rec.indices[j] = qp.indices[j];
-      QuadCand qcand;
-      for (int j = 0; j < 4; j++) {  // AdjustPixelCenters, quad_decimate 2
-        const float x = ok ? (qc[j][0] - 0.5f) * 2.0f + 0.5f : 0.f;
-        const float y = ok ? (qc[j][1] - 0.5f) * 2.0f + 0.5f : 0.f;
-        rec.corners[j][0] = qcand.p[j][0] = x;
-        rec.corners[j][1] = qcand.p[j][1] = y;
+      const bool live = src >= 0;
+      const uint32_t w = __shfl(wl, live ? src : 0);
+      const uint32_t f = w >> 16, rank = w & 0xffff;
+      const size_t slot = (size_t)f * kMaxPairs + rank;
+      if (live) {
+        const uint4* rec4 = reinterpret_cast<const uint4*>(b.fpend + slot);
+        uint4* lds4 = reinterpret_cast<uint4*>(&R.rec);
+        for (int j = rl; j < (int)(sizeof(FitPend) / 16); j += 16) lds4[j] = rec4[j];
       }
-      rec.accepted = ok;
-      if (prm.taps) b.quads[slot] = rec;  // (debug record: AT_STAGE_QUADS with the taps on)
-      if (ok && !AT_DIAG_STOP(prm, 5)) {
-        qcand.frame = f;
-        qcand.rank = rank;
-        const uint32_t ci = atomicAdd(b.nqcand + (size_t)f * kQcStride, 1u);
-        if (ci < (uint32_t)kQuadCandPerFrame) b.qcand[(size_t)f * kQuadCandPerFrame + ci] = qcand;
-        else atomicOr(b.status + f, kStatusQuadsOverflow);
+      wave_sync();
+      const uint32_t n = live ? R.rec.n : 0;
+      const int cnt = live ? (int)R.rec.cnt : 0;
+      // every segment a combination of the top cn = min(cnt, 10) peaks can use, fitted once
+      // (FitLine on the same moments as QuadFitCalculator's per-combination fits: identical
+      // results): the forward ones, then the closing ones (73 for 10 peaks: five row rounds)
+      const int cn = min(cnt, kNMaxima);
+      const int nfwd = cnt >= 4 ? cn * (cn - 1) / 2 : 0;
+      const int nfit = cnt >= 4 ? nfwd + (cn - 3) * (cn - 2) / 2 : 0;
+      for (int ci = rl; ci < nfit; ci += 16) {
+        const uint32_t ab = s_pair[ci < nfwd ? ci : kFitFwd + ci - nfwd];
+        const int a = (int)(ab & 0xff), bb = (int)(ab >> 8);
+        const Moments mo = seg_moments(R.rec, n, a, bb);
+        LineFitOut o;
+        o.p23[0] = o.p23[1] = 0.0;
+        if (ci < nfwd) o = fit_line_v<false, true>(mo);
+        else fit_line(mo, nullptr, nullptr, &o.err, &o.mse);
+        R.seg.put(a, bb, o);
       }
+      wave_sync();
+      if (AT_DIAG_STOP(prm, 7)) continue;
+      double err = DBL_MAX;
+      uint32_t bt = 0xffffffffu;
+      const int ncomb = num_combos(cnt);
+      for (int cj = rl; cj < ncomb; cj += 16) {
+        const int ci = (int)s_combo[210 + cj];
+        const double e4 = combo_err(R.seg, s_combo[ci], mse_max, prm.cos_critical_rad);
+        if (bt == 0xffffffffu || e4 < err || (e4 == err && (uint32_t)ci < bt)) { err = e4; bt = (uint32_t)ci; }
+      }
+      // MinQuadError over the row: minimum error, first (lowest) combination on ties
+#pragma unroll
+      for (int d = 8; d > 0; d >>= 1) {
+        const double oe = __shfl_xor(err, d);
+        const uint32_t ot = __shfl_xor(bt, d);
+        if (oe < err || (oe == err && ot < bt)) { err = oe; bt = ot; }
+      }
+      if (AT_DIAG_STOP(prm, 8)) continue;
+      if (bt >= 210) bt = 0;
+      const bool valid = live && err < (double)(prm.max_line_fit_mse * (float)n);
+      const uint32_t cbt = s_combo[bt];
+      if (live && rl < 4) {  // (a row's lanes 0-3 share the item: every shuffle below reads an active lane)
+        float cx = 0.f, cy = 0.f;
+        int bad = 0;
+        {
+          double l[4] = {0, 0, 0, 0};
+          if (valid) {  // side line k: fit_line's p01 and p23 from its d, c and centroid
+            float pre[4];
+            double e_, m_;
+            fit_line(seg_moments(R.rec, n, (cbt >> (8 * k)) & 0xff, (cbt >> (8 * ((k + 1) & 3))) & 0xff), nullptr, nullptr, &e_,
+                     &m_, pre);
+            l[0] = (double)pre[2];
+            l[1] = (double)pre[3];
+            line_normal(pre[0], pre[1], det_hypotf(pre[0], pre[1]), l + 2);
+          }
+          double m[4];
+#pragma unroll
+          for (int j = 0; j < 4; j++) m[j] = from(l[j], (k + 1) & 3);  // line k+1
+          if (valid) {
+            const double A00 = l[3], A01 = -m[3];
+            const double A10 = -l[2], A11 = m[2];
+            const double B0 = -l[0] + m[0];
+            const double B1 = -l[1] + m[1];
+            const double det = A00 * A11 - A10 * A01;
+            const double W00 = A11 / det, W01 = -A01 / det;
+            if (fabs(det) < 0.001) {
+              bad = 1;
+            } else {
+              const double L0 = W00 * B0 + W01 * B1;
+              cx = (float)(l[0] + L0 * A00);
+              cy = (float)(l[1] + L0 * A10);
+            }
+          }
+        }
+        bool ok = valid && !quad_or(bad);
+        float qc[4][2];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          qc[j][0] = fromf(cx, j);
+          qc[j][1] = fromf(cy, j);
+        }
+        // (corner i of a lane's own choosing by shuffle: a runtime index would put qc in scratch)
+        auto qx = [&](int i) { return fromf(cx, i); };
+        auto qy = [&](int i) { return fromf(cy, i); };
+        if (ok) {
+          // sides of triangles (0,1,2) and (2,3,0): 0->1, 1->2, 2->0, 2->3, 3->0, 0->2;
+          // lane k side k, lanes 0 and 1 also side 4 + k
+          auto side = [&](int j) {
+            const int a2 = j == 0 ? 0 : j == 1 ? 1 : j == 2 ? 2 : j == 3 ? 2 : j == 4 ? 3 : 0;
+            const int b2 = j == 0 ? 1 : j == 1 ? 2 : j == 2 ? 0 : j == 3 ? 3 : j == 4 ? 0 : 2;
+            return det_hypotf(qx(b2) - qx(a2), qy(b2) - qy(a2));
+          };
+          const float s0 = side(k), s1 = side(4 + (k & 1));
+          float len[6];
+#pragma unroll
+          for (int j = 0; j < 4; j++) len[j] = fromf(s0, j);
+          len[4] = fromf(s1, 0);
+          len[5] = fromf(s1, 1);
+          float area = 0, pp;
+          pp = (len[0] + len[1] + len[2]) / 2;
+          area += sqrtf(pp * (pp - len[0]) * (pp - len[1]) * (pp - len[2]));
+          pp = (len[3] + len[4] + len[5]) / 2;
+          area += sqrtf(pp * (pp - len[3]) * (pp - len[4]) * (pp - len[5]));
+          if ((double)area < 0.95 * g.min_tag_width * g.min_tag_width) ok = false;
+        }
+        if (ok) {
+          const int i0 = k, i1 = (i0 + 1) & 3, i2 = (i0 + 2) & 3;
+          const float dx1 = qx(i1) - qx(i0), dy1 = qy(i1) - qy(i0);
+          const float dx2 = qx(i2) - qx(i1), dy2 = qy(i2) - qy(i1);
+          const float cosd = (dx1 * dx2 + dy1 * dy2) / sqrtf((dx1 * dx1 + dy1 * dy1) * (dx2 * dx2 + dy2 * dy2));
+          const int abad = (double)fabsf(cosd) > prm.cos_critical_rad || dx1 * dy2 < dy1 * dx2;
+          if (quad_or(abad)) ok = false;
+        }
+        if (k == 0) {
+          QuadRecord rec;
+          rec.blob_index = R.rec.blob_index;
+          rec.valid = valid;
+          for (int j = 0; j < 4; j++) rec.indices[j] = R.rec.pi[(cbt >> (8 * j)) & 0xff];
+          QuadCand qcand;
+          for (int j = 0; j < 4; j++) {  // AdjustPixelCenters, quad_decimate 2
+            const float x = ok ? (qc[j][0] - 0.5f) * 2.0f + 0.5f : 0.f;
+            const float y = ok ? (qc[j][1] - 0.5f) * 2.0f + 0.5f : 0.f;
+            rec.corners[j][0] = qcand.p[j][0] = x;
+            rec.corners[j][1] = qcand.p[j][1] = y;
+          }
+          rec.accepted = ok;
+          if (prm.taps) b.quads[slot] = rec;  // (debug record: AT_STAGE_QUADS with the taps on)
+          if (ok && !AT_DIAG_STOP(prm, 5)) {
+            qcand.frame = f;
+            qcand.rank = rank;
+            const uint32_t ci = atomicAdd(b.nqcand + (size_t)f * kQcStride, 1u);
+            if (ci < (uint32_t)kQuadCandPerFrame) b.qcand[(size_t)f * kQuadCandPerFrame + ci] = qcand;
+            else atomicOr(b.status + f, kStatusQuadsOverflow);
+          }
+        }
+      }
+      wave_sync();  // (the row's LDS is read until here; the next group rewrites it)
     }
   }
 }
@@ -7661,13 +7830,14 @@ hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, i
     else hipLaunchKernelGGL(k_blob_small<false>, dim3(prm.sblob_wg ? prm.sblob_wg : nblobwg * 2), dim3(256), 0, s, b, g, prm, g.nlarge, kNumCls, 0);
     tk(8, s, 1);
   };
-  // the side fits of the blobs the throughput-mode (non-FUSE) blob kernels fitted:
-  // every class, or (latency mode above 4096-point blobs) the large classes only.  In
-  // the stage profile it counts with k_blob; the kernel timer's k_blob span leaves it out
+  // FitQuads of the blobs the non-FUSE blob kernels handed over: every class, or (latency
+  // mode above 4096-point blobs) the large classes only.  In the stage profile it counts
+  // with k_blob; the kernel timer's k_blob span leaves it out
   const int fin_c1 = g.ctw != 32 ? kNumCls : g.max_cluster > 4096 ? g.nlarge : 0;
   auto quad_fin = [&](hipStream_t s) {
-    if (fin_c1 > 0 && on(9) && (!AT_DIAG_ANY(prm) || AT_DIAG_STOP(prm, 5)))  // (a blob-phase cut leaves no side moments)
-      hipLaunchKernelGGL(k_quad_fin, dim3(std::max(1, std::min(2048, 8 * B))), dim3(256), 0, s, b, g, prm, 0, fin_c1);
+    // (a blob-phase cut before the prefix lookups leaves no hand-over records; cuts 7 and 8 are k_fit_quads' own)
+    if (fin_c1 > 0 && on(9) && (!AT_DIAG_ANY(prm) || AT_DIAG_STOP(prm, 5) || AT_DIAG_STOP(prm, 7) || AT_DIAG_STOP(prm, 8)))
+      hipLaunchKernelGGL(k_fit_quads, dim3(std::max(1, std::min(2048, 8 * B))), dim3(256), 0, s, b, g, prm, 0, fin_c1);
   };
   if (ev || !st2 || lat_fused) {
     blob_small(st);
