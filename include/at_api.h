@@ -820,6 +820,98 @@ int at_camcal_set_profiling(at_camcal *c, int on);
 int at_camcal_stats(const at_camcal *c, uint64_t *out, int cap);
 void at_camcal_destroy(at_camcal *c);
 
+/* Field map: where the tags of a field really stand, from recorded views (bundle adjustment).
+ *
+ * A map is 1..AT_FIELDMAP_MAX_TAGS tags.  Each carries an at_field_tag (x_field = R x_tag + t), a
+ * flag `known` (1: the given pose is its start, 0: there is none and R, t are not read) and the
+ * flags free_rot / free_trans of what is to be solved for.  At least one tag must be known with
+ * both flags 0: the anchor, which fixes where the field frame is.
+ * Unknowns: the camera pose of every stored view that takes part (x_cam = R x_field + t) and the
+ * free parts of every placed tag.  Cost: the summed squared error in pixels of every stored corner
+ * of every placed tag against at_detection.p through the view's own fx, fy, cx, cy (p as k_pose
+ * reads it: no further undistortion); a corner at Pz <= 0 costs infinity.  Parameters: per view
+ * (w, dt) as the field pose (w left-multiplied, t' = t + dt); per tag (w_j, d_j) with
+ * R_j' = R_j dR(w_j), t_j' = t_j + d_j.  16 Levenberg-Marquardt iterations on the whole problem
+ * through the Schur complement of the views' 6 x 6 pose blocks, the reduced system (6 per tag)
+ * assembled sparsely, block pair by block pair; lambda from 1e-3, / 10 (floor 1e-9) on an accepted
+ * step (the total cost fell and every Pz stayed positive), x 10 on a rejected one; a reduced
+ * system without a Cholesky factor is a rejected iteration.  A part that is not free comes back
+ * bit for bit.
+ * Placing: a tag with known = 0 gets its start from views that see it together with tags already
+ * placed, in rounds over ascending ids until nothing changes: per such view the camera pose by
+ * the field pose's start rule over the view's placed tags, the candidate (cam_T_field)^-1
+ * cam_T_tag, and of all candidates the one with the least summed squared reprojection error of the
+ * tag's corners over all such views (ties: the lower view).  A tag no chain of views reaches is
+ * not placed: placed = 0 and zeros in its record, and its observations take no part.
+ * Every view starts from the field pose's solve over the placed tags' start poses; one that gets
+ * none is skipped.  A component of the map without a fixed tag is not refused: it floats where
+ * its start put it and its variances mean nothing (at_fieldmap.h).
+ *
+ * at_fieldmap_create: AT_E_INVALID for a NULL, n outside 1..AT_FIELDMAP_MAX_TAGS, an id outside
+ * [0, 1024) or twice, no anchor, a known tag at_set_field_layout would refuse, max_hamming < 0,
+ * tag_size not positive.
+ * at_fieldmap_add: one frame's at_detections / at_poses arrays and that frame's camera (fx, fy,
+ * cx, cy are kept); the field pose's selection over the map's ids is stored (at most
+ * AT_FIELD_MAX_TAGS tags, the lowest ids: id, corners, the tag's own pose).  Returns 1 if stored,
+ * 0 if fewer than two map tags were selected (such a view constrains nothing), AT_E_CAPACITY
+ * beyond AT_FIELDMAP_MAX_VIEWS.
+ * at_fieldmap_solve: the solve on the GPU (kernels k_fm_*, on a stream of the mapper's own; one
+ * synchronisation, at the end; it is in no detector's launch sequence and writes nothing of a
+ * detector's).  at_fieldmap_solve_host: the same on the CPU, the kernels' arithmetic in the
+ * kernels' order: bit-equal records.  Both AT_E_INVALID without a stored view.
+ * cov of a tag is sigma^2 times its 6 x 6 diagonal block of the inverse of the undamped reduced
+ * matrix at the final state, order (w_j, d_j) -- w_j a small turn in the tag frame, d_j in the
+ * field frame -- sigma^2 = cost / (2 corners - 6 views_used - free parameters); rows and columns
+ * of parameters that are not free are zero; cov_valid = 0 (and zeros) without a factor or with a
+ * denominator that is not positive.
+ * at_fieldmap_tags: per tag of the map, in the order given, of the last solve; at_fieldmap_views:
+ * per stored view, its final camera pose and RMS (used = 0: skipped, rest zero).  Both return the
+ * count and write at most cap.
+ * at_fieldmap_stats, the last solve: [0] views used, [1] skipped, [2] accepted steps, [3] rejected
+ * steps, [4] the kernels' time in nanoseconds (HIP events around the sequence of the last
+ * at_fieldmap_solve while at_fieldmap_set_profiling is on, 0 otherwise), [5] candidates dropped by
+ * the 16-tag cap over the stored views. */
+#define AT_FIELDMAP_MAX_TAGS 32
+#define AT_FIELDMAP_MAX_VIEWS 4096
+typedef struct {
+  at_field_tag tag;
+  int32_t known;
+  int32_t free_rot, free_trans;
+  int32_t pad;
+} at_fieldmap_tag;
+typedef struct {
+  int32_t id, placed;
+  double R[9]; double t[3];            /* x_field = R x_tag + t, final */
+  double R0[9]; double t0[3];          /* the start: where the caller or the chain put it */
+  double cov[36];
+  int32_t views, pad;                  /* stored views that hold the tag */
+} at_fieldmap_tag_result;
+typedef struct {
+  double rms_before, rms_after;        /* pixels, over the corners of the views used */
+  int32_t views_used, views_skipped;
+  int32_t corners;
+  int32_t accepted, rejected;
+  int32_t cov_valid;
+  int32_t n_tags, n_placed;
+} at_fieldmap_result;
+typedef struct {
+  double R[9]; double t[3];            /* x_cam = R x_field + t */
+  double rms_px;
+  int32_t n_tags, used;
+} at_fieldmap_view;
+typedef struct at_fieldmap at_fieldmap;
+int at_fieldmap_create(const at_fieldmap_tag *tags, int n, int max_hamming, double tag_size, at_fieldmap **out);
+int at_fieldmap_add(at_fieldmap *m, const at_detection *dets, const at_pose *poses, int n, const at_camera *cam);
+int at_fieldmap_count(const at_fieldmap *m);
+int at_fieldmap_clear(at_fieldmap *m);
+int at_fieldmap_solve(at_fieldmap *m, at_fieldmap_result *out);
+int at_fieldmap_solve_host(at_fieldmap *m, at_fieldmap_result *out);
+int at_fieldmap_tags(const at_fieldmap *m, at_fieldmap_tag_result *out, int cap);
+int at_fieldmap_views(const at_fieldmap *m, at_fieldmap_view *out, int cap);
+int at_fieldmap_set_profiling(at_fieldmap *m, int on);
+int at_fieldmap_stats(const at_fieldmap *m, uint64_t *out, int cap);
+void at_fieldmap_destroy(at_fieldmap *m);
+
 /* Page-locked host memory (hipHostMalloc) for buffers the detector copies into on
  * its stream by DMA, e.g. at_annotate_staged's bgr_out: a pageable destination
  * goes through the runtime's staging buffers instead.  (No counterpart in the

@@ -26,6 +26,7 @@
 #include "at_mjpg_entropy.h"
 #include "at_preview.h"
 #include "at_rigcal.h"
+#include "at_fieldmap.h"
 #include "at_camcal.h"
 
 namespace at {
@@ -59,6 +60,7 @@ void rig_write(const RigRecord& r, at_rig_pose* o);
 hipError_t launch_rig(const RigBufs& rb, int ninstants, hipStream_t st);
 hipError_t launch_rigcal(const CalBufs& b, hipStream_t st);
 hipError_t launch_camcal(const CcBufs& b, hipStream_t st);
+hipError_t launch_fieldmap(const FmBufs& b, hipStream_t st);
 
 struct CodeEntry {
   int id;
@@ -2617,6 +2619,175 @@ int at_camcal_solve(at_camcal* c, at_camcal_result* out) {
   const int w = g->h_ctl->which & 1;
   cc_finish(c, *g->h_ctl, g->h_cam[w], g->h_cov, g->h_pose[w], g->h_viewcost, g->h_ntags, out);
   c->ns = ns;
+  return AT_OK;
+}
+
+// ---- field map -----------------------------------------------------------------
+// The device side of an at_fieldmap (at_fieldmap.cpp holds the rest), as CalGpu: a stream and two
+// events of its own, the stored views in HBM, the solve's buffers sized for the views stored so
+// far (grown by doubling; those of the reduced system depend on the map's tag count only), and
+// pinned host memory for what goes up and comes back.
+namespace at {
+struct FmGpu {
+  int device;
+  hipStream_t st;
+  hipEvent_t ev[2];
+  int cap_n;  // views the buffers hold
+  std::vector<void*> dev, host;
+  FmBufs b;  // device pointers
+  CalPose *h_pose[2], *h_tag[2], *h_start;
+  int16_t* h_lut;
+  FpTag* h_lay;
+  double *h_viewcost, *h_cov;
+  int32_t* h_ntags;
+  CalCtl* h_ctl;
+};
+}  // namespace at
+
+static void fmgpu_release(FmGpu* g) {
+  for (void* p : g->dev) (void)hipFree(p);
+  for (void* p : g->host) (void)hipHostFree(p);
+  g->dev.clear();
+  g->host.clear();
+  g->cap_n = 0;
+}
+
+static void fmgpu_free(FmGpu* g) {
+  if (!g) return;
+  (void)hipSetDevice(g->device);
+  if (g->st) (void)hipStreamSynchronize(g->st);
+  fmgpu_release(g);
+  for (hipEvent_t e : g->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (g->st) (void)hipStreamDestroy(g->st);
+  delete g;
+}
+
+static int fmgpu_reserve(at_fieldmap* m, FmGpu* g, int n) {
+  if (hipStreamSynchronize(g->st) != hipSuccess) return AT_E_HIP;
+  fmgpu_release(g);
+  bool ok = true;
+  auto dmal = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (!ok || hipMalloc(&p, bytes) != hipSuccess) {
+      ok = false;
+      return nullptr;
+    }
+    g->dev.push_back(p);
+    return p;
+  };
+  auto hmal = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (!ok || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+      ok = false;
+      return nullptr;
+    }
+    g->host.push_back(p);
+    return p;
+  };
+  FmBufs& b = g->b;
+  memset(&b, 0, sizeof(b));
+  b.T = m->n_tags;
+  b.N = n;
+  const size_t N = (size_t)n, T = (size_t)m->n_tags, E = (size_t)b.E(), M = (size_t)b.M();
+  b.obs = (const FmObs*)dmal(N * sizeof(FmObs));
+  b.rec = (FpRecord*)dmal(N * sizeof(FpRecord));
+  b.ntags = (int32_t*)dmal(N * sizeof(int32_t));
+  for (int q = 0; q < 2; q++) {
+    b.pose[q] = (CalPose*)dmal(N * sizeof(CalPose));
+    b.tag[q] = (CalPose*)dmal(T * sizeof(CalPose));
+    g->h_pose[q] = (CalPose*)hmal(N * sizeof(CalPose));
+    g->h_tag[q] = (CalPose*)hmal(T * sizeof(CalPose));
+  }
+  b.view = (double*)dmal(N * kFmViewLen * sizeof(double));
+  b.tab = (int32_t*)dmal(N * kFpMaxTags * sizeof(int32_t));
+  b.inv = (int32_t*)dmal(N * kFmMaxTags * sizeof(int32_t));
+  b.chunk = (double*)dmal((size_t)b.chunks() * E * sizeof(double));
+  b.S = (double*)dmal(E * sizeof(double));
+  b.A = (double*)dmal(M * M * sizeof(double));
+  b.dc = (double*)dmal(M * sizeof(double));
+  b.viewcost = (double*)dmal(N * sizeof(double));
+  b.cov = (double*)dmal(T * 36 * sizeof(double));
+  b.ctl = (CalCtl*)dmal(sizeof(CalCtl));
+  b.lay.lut = (const int16_t*)dmal(kFpMaxIds * sizeof(int16_t));
+  b.lay.tags = (const FpTag*)dmal(T * sizeof(FpTag));
+  b.lay.max_hamming = m->max_hamming;
+  g->h_start = (CalPose*)hmal(T * sizeof(CalPose));
+  g->h_lut = (int16_t*)hmal(kFpMaxIds * sizeof(int16_t));
+  g->h_lay = (FpTag*)hmal(T * sizeof(FpTag));
+  g->h_viewcost = (double*)hmal(N * sizeof(double));
+  g->h_cov = (double*)hmal(T * 36 * sizeof(double));
+  g->h_ntags = (int32_t*)hmal(N * sizeof(int32_t));
+  g->h_ctl = (CalCtl*)hmal(sizeof(CalCtl));
+  if (!ok) {
+    fmgpu_release(g);
+    return AT_E_NOMEM;
+  }
+  g->cap_n = n;
+  m->obs_dirty = true;
+  return AT_OK;
+}
+
+int at_fieldmap_solve(at_fieldmap* m, at_fieldmap_result* out) {
+  if (!m || !out || m->n < 1) return AT_E_INVALID;
+  FmGpu* g = m->gpu;
+  if (!g) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return AT_E_HIP;
+    g = new FmGpu();
+    g->device = dev;
+    bool ok = hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; i < 2 && ok; i++) ok = hipEventCreateWithFlags(&g->ev[i], kTimingEventFlags) == hipSuccess;
+    if (!ok) {
+      fmgpu_free(g);
+      return AT_E_HIP;
+    }
+    m->gpu = g;
+    m->gpu_free = fmgpu_free;
+  }
+  if (hipSetDevice(g->device) != hipSuccess) return AT_E_HIP;
+  if (m->n > g->cap_n) {
+    const int rc = fmgpu_reserve(m, g, std::min(kFmMaxViews, std::max(m->n, 2 * g->cap_n)));
+    if (rc != AT_OK) return rc;
+  }
+  // (the buffers may hold more views than are stored: no stride depends on the count)
+  FmBufs b = g->b;
+  const FpLayout lay = b.lay;
+  std::vector<int32_t> seen((size_t)m->n_tags);
+  fm_prepare(*m, &b, g->h_start, g->h_lut, g->h_lay, seen.data());
+  b.lay = lay;
+  const size_t N = (size_t)m->n, T = (size_t)m->n_tags;
+  if (m->obs_dirty) {
+    HIPCHK(hipMemcpyAsync((void*)b.obs, m->obs.data(), N * sizeof(FmObs), hipMemcpyHostToDevice, g->st));
+    m->obs_dirty = false;
+  }
+  HIPCHK(hipMemcpyAsync((void*)b.lay.lut, g->h_lut, kFpMaxIds * sizeof(int16_t), hipMemcpyHostToDevice, g->st));
+  HIPCHK(hipMemcpyAsync((void*)b.lay.tags, g->h_lay, T * sizeof(FpTag), hipMemcpyHostToDevice, g->st));
+  for (int q = 0; q < 2; q++)
+    HIPCHK(hipMemcpyAsync(b.tag[q], g->h_start, T * sizeof(CalPose), hipMemcpyHostToDevice, g->st));
+  HIPCHK(hipMemsetAsync(b.ctl, 0, sizeof(CalCtl), g->st));
+  if (m->profiling) HIPCHK(hipEventRecord(g->ev[0], g->st));
+  HIPCHK(launch_fieldmap(b, g->st));
+  if (m->profiling) HIPCHK(hipEventRecord(g->ev[1], g->st));
+  HIPCHK(hipMemcpyAsync(g->h_ctl, b.ctl, sizeof(CalCtl), hipMemcpyDeviceToHost, g->st));
+  for (int q = 0; q < 2; q++) {
+    HIPCHK(hipMemcpyAsync(g->h_tag[q], b.tag[q], T * sizeof(CalPose), hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipMemcpyAsync(g->h_pose[q], b.pose[q], N * sizeof(CalPose), hipMemcpyDeviceToHost, g->st));
+  }
+  HIPCHK(hipMemcpyAsync(g->h_cov, b.cov, T * 36 * sizeof(double), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(g->h_viewcost, b.viewcost, N * sizeof(double), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(g->h_ntags, b.ntags, N * sizeof(int32_t), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipStreamSynchronize(g->st));
+  uint64_t ns = 0;
+  if (m->profiling) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
+    ns = (uint64_t)((double)ms * 1e6);
+  }
+  const int w = g->h_ctl->which & 1;
+  fm_finish(m, b, *g->h_ctl, g->h_start, seen.data(), g->h_tag[w], g->h_cov, g->h_pose[w], g->h_viewcost, g->h_ntags,
+            out);
+  m->ns = ns;
   return AT_OK;
 }
 

@@ -30,6 +30,7 @@
 #include "at_mjpg_entropy.h"
 #include "at_pose.h"
 #include "at_rigcal.h"
+#include "at_fieldmap.h"
 #include "at_camcal.h"
 
 
@@ -6417,6 +6418,107 @@ hipError_t launch_camcal(const CcBufs& b, hipStream_t st) {
     hipLaunchKernelGGL(k_cc_decide, one, team, 0, st, b, 1);
   }
   hipLaunchKernelGGL(k_cc_back, per_view, wave, 0, st, b, 0);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Field map (at_fieldmap_solve): where the tags of a map stand, from N stored views; the algorithm
+// is at_fieldmap.h's, which at_fieldmap_solve_host runs with one thread.  The per-view kernels
+// (k_fm_start, k_fm_accum, k_fm_back) are one workgroup of one wave per view, one lane per corner
+// slot, like k_field and k_cc_*: U and g cross the wave by the halving butterfly into LDS, a tag's
+// 63 sums cross its quad of lanes by two xor shuffles (2, then 1: the last two steps of the same
+// tree), and the 97 columns of Y and y are solved 64 lanes at a time.  A view keeps kFmViewLen
+// doubles (12.9 KB) and two small tables (written once, by k_fm_start) in HBM, whatever the size
+// of the map.  k_fm_reduce is the sparse assembly: one 64-lane workgroup per (block pair or tag, chunk of 32 views), lane e < 36
+// one entry of the pair's 6 x 6 block; every lane walks the chunk's views in order and passes over
+// those that do not hold both tags (the branch is uniform over the workgroup).  k_fm_total adds
+// the chunk sums, one thread per entry.  k_fm_solve is one workgroup of 256: the packed lower
+// triangle of the 192 x 192 matrix, factored in place, lives in dynamic LDS (148 KB at 32 tags,
+// beside 11 KB of vectors: the CU's 160 KB; there is no other form, DESIGN 7k has the time of the
+// L2 form it replaced).
+// k_fm_decide leaves the accept / reject word (CalCtl::which) that the
+// next iteration's kernels read from HBM.  Branches around barriers depend on b.ntags[i], CalCtl
+// and the sizes only: uniform over a workgroup.
+// ---------------------------------------------------------------------------
+struct FmTeam : CalTeam {
+  // the sum over the quad of lanes of a tag: (c0 + c2) + (c1 + c3) in every lane of it
+  __device__ void quad(const double* v, double* o) const {
+    const double a = v[0] + __shfl_xor(v[0], 2);
+    o[0] = a + __shfl_xor(a, 1);
+  }
+};
+__device__ inline FmTeam fm_team() {
+  FmTeam tm;
+  tm.tid = (int)threadIdx.x;
+  tm.nt = (int)blockDim.x;
+  return tm;
+}
+__global__ __launch_bounds__(64) void k_fm_start(FmBufs b) {
+  const int i = (int)blockIdx.x;
+  if (i >= b.N) return;
+  fm_start(fm_team(), b, i);
+}
+__global__ __launch_bounds__(64) void k_fm_accum(FmBufs b, int final) {
+  __shared__ FmShared sh;
+  const int i = (int)blockIdx.x;
+  if (i >= b.N) return;
+  fm_accum(fm_team(), sh, b, i, final != 0);
+}
+__global__ __launch_bounds__(64) void k_fm_reduce(FmBufs b) {
+  const int item = (int)blockIdx.x, ch = (int)blockIdx.y, e = (int)threadIdx.x;
+  if (item >= b.pairs() + b.T || ch >= b.chunks()) return;
+  if (e >= (item < b.pairs() ? 36 : 12)) return;
+  fm_chunk_entry(b, ch, item, e);
+}
+__global__ __launch_bounds__(256) void k_fm_total(FmBufs b) {
+  const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (e >= b.E()) return;
+  fm_total(b, e);
+}
+// the packed triangle in dynamic LDS: M (M + 1) / 2 doubles, 148,224 B at M = 192, beside the 11 KB
+// of vectors
+__global__ __launch_bounds__(256) void k_fm_solve(FmBufs b, int final) {
+  __shared__ FmSolveShared sh;
+  extern __shared__ double fm_triangle[];
+  fm_solve(fm_team(), sh, b, fm_triangle, final != 0);
+}
+__global__ __launch_bounds__(64) void k_fm_back(FmBufs b, int step) {
+  __shared__ FmShared sh;
+  const int i = (int)blockIdx.x;
+  if (i >= b.N) return;
+  fm_back(fm_team(), sh, b, i, step != 0);
+}
+__global__ __launch_bounds__(256) void k_fm_decide(FmBufs b, int step) {
+  __shared__ FmSolveShared sh;
+  fm_decide(fm_team(), sh, b, step != 0);
+}
+// the whole solve, in order on st: start, the start's cost, kFmIters iterations, the covariance
+// pass and the final per-view costs
+hipError_t launch_fieldmap(const FmBufs& b, hipStream_t st) {
+  const dim3 per_view(b.N), wave(64), one(1), team(256);
+  const dim3 items(b.pairs() + b.T, b.chunks()), entries((b.E() + 255) / 256);
+  // the triangle's LDS: beyond 64 KB the kernel's limit has to be raised first; a device that does
+  // not grant a workgroup that much (gfx950 grants 160 KB) is an error, there is no other form
+  const size_t tri_bytes = (size_t)b.M() * (b.M() + 1) / 2 * sizeof(double);
+  if (tri_bytes + sizeof(FmSolveShared) > 65536) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fm_solve),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)tri_bytes);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_fm_start, per_view, wave, 0, st, b);
+  hipLaunchKernelGGL(k_fm_back, per_view, wave, 0, st, b, 0);
+  hipLaunchKernelGGL(k_fm_decide, one, team, 0, st, b, 0);
+  for (int it = 0; it <= kFmIters; it++) {
+    const int final = it == kFmIters;
+    hipLaunchKernelGGL(k_fm_accum, per_view, wave, 0, st, b, final);
+    hipLaunchKernelGGL(k_fm_reduce, items, wave, 0, st, b);
+    hipLaunchKernelGGL(k_fm_total, entries, team, 0, st, b);
+    hipLaunchKernelGGL(k_fm_solve, one, team, tri_bytes, st, b, final);
+    if (final) break;
+    hipLaunchKernelGGL(k_fm_back, per_view, wave, 0, st, b, 1);
+    hipLaunchKernelGGL(k_fm_decide, one, team, 0, st, b, 1);
+  }
+  hipLaunchKernelGGL(k_fm_back, per_view, wave, 0, st, b, 0);
   return hipGetLastError();
 }
 

@@ -50,9 +50,14 @@ EXPORTS = [
     "at_rigcal_solve_host", "at_rigcal_instants", "at_rigcal_set_profiling", "at_rigcal_stats", "at_rigcal_destroy",
     "at_camcal_create", "at_camcal_add", "at_camcal_count", "at_camcal_clear", "at_camcal_solve",
     "at_camcal_solve_host", "at_camcal_views", "at_camcal_set_profiling", "at_camcal_stats", "at_camcal_destroy",
+    "at_fieldmap_create", "at_fieldmap_add", "at_fieldmap_count", "at_fieldmap_clear", "at_fieldmap_solve",
+    "at_fieldmap_solve_host", "at_fieldmap_tags", "at_fieldmap_views", "at_fieldmap_set_profiling",
+    "at_fieldmap_stats", "at_fieldmap_destroy",
 ]
 AT_RIGCAL_MAX_INSTANTS = 4096
 AT_CAMCAL_MAX_VIEWS = 4096
+AT_FIELDMAP_MAX_TAGS = 32
+AT_FIELDMAP_MAX_VIEWS = 4096
 # at_camcal_config.free_mask bits, in at_camera's order
 CAMCAL_PARAMS = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")
 (AT_CAMCAL_FX, AT_CAMCAL_FY, AT_CAMCAL_CX, AT_CAMCAL_CY, AT_CAMCAL_K1, AT_CAMCAL_K2, AT_CAMCAL_P1, AT_CAMCAL_P2,
@@ -159,6 +164,28 @@ class AtCamcalResult(C.Structure):
 
 
 class AtCamcalView(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("rms_px", C.c_double), ("n_tags", C.c_int32),
+                ("used", C.c_int32)]
+
+
+class AtFieldmapTag(C.Structure):
+    _fields_ = [("tag", AtFieldTag), ("known", C.c_int32), ("free_rot", C.c_int32), ("free_trans", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class AtFieldmapTagResult(C.Structure):
+    _fields_ = [("id", C.c_int32), ("placed", C.c_int32), ("R", C.c_double * 9), ("t", C.c_double * 3),
+                ("R0", C.c_double * 9), ("t0", C.c_double * 3), ("cov", C.c_double * 36), ("views", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class AtFieldmapResult(C.Structure):
+    _fields_ = [("rms_before", C.c_double), ("rms_after", C.c_double), ("views_used", C.c_int32),
+                ("views_skipped", C.c_int32), ("corners", C.c_int32), ("accepted", C.c_int32),
+                ("rejected", C.c_int32), ("cov_valid", C.c_int32), ("n_tags", C.c_int32), ("n_placed", C.c_int32)]
+
+
+class AtFieldmapView(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("rms_px", C.c_double), ("n_tags", C.c_int32),
                 ("used", C.c_int32)]
 
@@ -289,6 +316,48 @@ class CameraCalibration:
 class CameraCalView:
     """at_camcal_view: the board's final pose in a stored view, x_cam = R x_board + t, and the view's
     RMS (used False: skipped)."""
+    R: np.ndarray
+    t: np.ndarray
+    rms_px: float
+    n_tags: int
+    used: bool
+
+
+@dataclass
+class FieldMap:
+    """at_fieldmap_result: the totals of a field-map solve (the tags are FieldMapper.tags())."""
+    rms_before: float
+    rms_after: float
+    views_used: int
+    views_skipped: int
+    corners: int
+    accepted: int
+    rejected: int
+    cov_valid: bool
+    n_tags: int
+    n_placed: int
+
+
+@dataclass
+class FieldMapTag:
+    """at_fieldmap_tag_result: a map tag's final pose x_field = R x_tag + t, its start (R0, t0: where
+    the caller or the chain of views put it) and the 6 x 6 covariance of (w, d) -- w a small turn in
+    the tag frame, d in the field frame; rows and columns of parameters that were not free are
+    zero.  placed False: no chain of views reached the tag, the rest is zero."""
+    id: int
+    placed: bool
+    R: np.ndarray
+    t: np.ndarray
+    R0: np.ndarray
+    t0: np.ndarray
+    cov: np.ndarray    # [6, 6]; zeros unless the solve's cov_valid
+    views: int         # stored views that hold the tag
+
+
+@dataclass
+class FieldMapView:
+    """at_fieldmap_view: a stored view's final camera pose, x_cam = R x_field + t, and its RMS
+    (used False: skipped)."""
     R: np.ndarray
     t: np.ndarray
     rms_px: float
@@ -488,6 +557,20 @@ def load_library(path: str = LIB_PATH):
         L.at_camcal_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
         L.at_camcal_destroy.argtypes = [C.c_void_p]
         L.at_camcal_destroy.restype = None
+    if hasattr(L, "at_fieldmap_solve"):  # (A/B builds of older sources lack the field map)
+        L.at_fieldmap_create.argtypes = [C.POINTER(AtFieldmapTag), C.c_int, C.c_int, C.c_double, C.POINTER(C.c_void_p)]
+        L.at_fieldmap_add.argtypes = [C.c_void_p, C.POINTER(AtDetection), C.POINTER(AtPose), C.c_int,
+                                      C.POINTER(AtCamera)]
+        for name in ("at_fieldmap_count", "at_fieldmap_clear"):
+            getattr(L, name).argtypes = [C.c_void_p]
+        for name in ("at_fieldmap_solve", "at_fieldmap_solve_host"):
+            getattr(L, name).argtypes = [C.c_void_p, C.POINTER(AtFieldmapResult)]
+        L.at_fieldmap_tags.argtypes = [C.c_void_p, C.POINTER(AtFieldmapTagResult), C.c_int]
+        L.at_fieldmap_views.argtypes = [C.c_void_p, C.POINTER(AtFieldmapView), C.c_int]
+        L.at_fieldmap_set_profiling.argtypes = [C.c_void_p, C.c_int]
+        L.at_fieldmap_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.at_fieldmap_destroy.argtypes = [C.c_void_p]
+        L.at_fieldmap_destroy.restype = None
     _LIB = L
     return L
 
@@ -1219,6 +1302,120 @@ class CameraCalibrator:
     def close(self):
         if getattr(self, "_h", None):
             load_library().at_camcal_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+# ---- field map (k_fm_*) -----------------------------------------------------------
+class FieldMapper:
+    """at_fieldmap: where the tags of a field stand, from recorded views.  `tags` is one
+    (id, R, t, free_rot, free_trans) per map tag -- its start x_field = R x_tag + t and which of the
+    two are to be solved for; R = None marks a tag without a start (known = 0), which is placed from
+    views that see it together with placed tags.  At least one tag must have a start and both flags
+    false: the anchor.  Raises FieldPoseError for arguments the library refuses."""
+
+    def __init__(self, tags, max_hamming=0, tag_size=TAG_SIZE):
+        L = load_library()
+        tags = list(tags)
+        n = len(tags)
+        arr = (AtFieldmapTag * max(1, n))()
+        for i, (tid, R, t, free_rot, free_trans) in enumerate(tags):
+            arr[i].tag.id = int(tid)
+            arr[i].known = int(R is not None)
+            if R is not None:
+                arr[i].tag.R[:] = [float(x) for x in np.asarray(R, np.float64).reshape(9)]
+                arr[i].tag.t[:] = [float(x) for x in np.asarray(t, np.float64).reshape(3)]
+            arr[i].free_rot, arr[i].free_trans = int(bool(free_rot)), int(bool(free_trans))
+        h = C.c_void_p()
+        self._h = None
+        rc = L.at_fieldmap_create(arr, n, int(max_hamming), float(tag_size), C.byref(h))
+        if rc < 0:
+            raise FieldPoseError("at_fieldmap_create", rc)
+        self._h = h
+
+    def add(self, dets, poses, camera_matrix=None):
+        """at_fieldmap_add: one frame's detections and poses (same order) and its camera's
+        CameraMatrix.  True if the view was stored, False if fewer than two map tags were in it.
+        FieldPoseError (AT_E_CAPACITY) beyond AT_FIELDMAP_MAX_VIEWS."""
+        dets, poses = list(dets), list(poses)
+        if len(dets) != len(poses):
+            raise ValueError("one pose per detection")
+        cam = camera_matrix or TEST_CAMERA
+        darr, n = _detection_records(dets)
+        parr = _pose_records(poses, n)
+        c = AtCamera(fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy)
+        rc = load_library().at_fieldmap_add(self._h, darr, parr, n, C.byref(c))
+        if rc < 0:
+            raise FieldPoseError("at_fieldmap_add", rc)
+        return bool(rc)
+
+    def __len__(self):
+        return int(load_library().at_fieldmap_count(self._h))
+
+    def clear(self):
+        _check(load_library().at_fieldmap_clear(self._h), "at_fieldmap_clear")
+
+    def _solve(self, name):
+        out = AtFieldmapResult()
+        rc = getattr(load_library(), name)(self._h, C.byref(out))
+        if rc < 0:
+            raise FieldPoseError(name, rc)
+        self.record = out
+        return FieldMap(rms_before=out.rms_before, rms_after=out.rms_after, views_used=out.views_used,
+                        views_skipped=out.views_skipped, corners=out.corners, accepted=out.accepted,
+                        rejected=out.rejected, cov_valid=bool(out.cov_valid), n_tags=out.n_tags,
+                        n_placed=out.n_placed)
+
+    def solve(self):
+        """at_fieldmap_solve: the solve on the GPU (the current device), on the mapper's own stream."""
+        return self._solve("at_fieldmap_solve")
+
+    def solve_host(self):
+        """at_fieldmap_solve_host: the same solve on the CPU, bit-equal records."""
+        return self._solve("at_fieldmap_solve_host")
+
+    def tag_records(self):
+        """The at_fieldmap_tag_result array of the last solve (the bit-exact view) and its length."""
+        L = load_library()
+        n = _check(L.at_fieldmap_tags(self._h, None, 0), "at_fieldmap_tags")
+        buf = (AtFieldmapTagResult * max(1, n))()
+        return buf, _check(L.at_fieldmap_tags(self._h, buf, n), "at_fieldmap_tags")
+
+    def tags(self):
+        """at_fieldmap_tags: one FieldMapTag per map tag of the last solve, in the order given."""
+        buf, n = self.tag_records()
+        return [FieldMapTag(id=b.id, placed=bool(b.placed), R=np.array(list(b.R)).reshape(3, 3), t=np.array(list(b.t)),
+                            R0=np.array(list(b.R0)).reshape(3, 3), t0=np.array(list(b.t0)),
+                            cov=np.array(list(b.cov)).reshape(6, 6), views=b.views) for b in buf[:n]]
+
+    def view_records(self):
+        """The at_fieldmap_view array of the last solve and its length."""
+        L = load_library()
+        n = _check(L.at_fieldmap_views(self._h, None, 0), "at_fieldmap_views")
+        buf = (AtFieldmapView * max(1, n))()
+        return buf, _check(L.at_fieldmap_views(self._h, buf, n), "at_fieldmap_views")
+
+    def views(self):
+        """at_fieldmap_views: one FieldMapView per stored view of the last solve."""
+        buf, n = self.view_records()
+        return [FieldMapView(R=np.array(list(b.R)).reshape(3, 3), t=np.array(list(b.t)), rms_px=b.rms_px,
+                             n_tags=b.n_tags, used=bool(b.used)) for b in buf[:n]]
+
+    def set_profiling(self, on=True):
+        _check(load_library().at_fieldmap_set_profiling(self._h, int(bool(on))), "at_fieldmap_set_profiling")
+
+    def stats(self):
+        """at_fieldmap_stats of the last solve."""
+        buf = (C.c_uint64 * 6)()
+        n = _check(load_library().at_fieldmap_stats(self._h, buf, len(buf)), "at_fieldmap_stats")
+        names = ("views_used", "views_skipped", "accepted_steps", "rejected_steps", "kernel_ns", "dropped")
+        return {k: int(v) for k, v in zip(names[:n], buf)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().at_fieldmap_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -140,6 +140,49 @@ def load_field_layout(layout):
             for tid, R, t in layout]
 
 
+def _rotation_quat(R):
+    """(w, x, y, z) of a rotation matrix, w >= 0: the largest-pivot extraction, normalised."""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0:
+        s = 2.0 * np.sqrt(tr + 1.0)
+        q = [0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s]
+    elif R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
+        s = 2.0 * np.sqrt(1.0 + R[0, 0] - R[1, 1] - R[2, 2])
+        q = [(R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s]
+    elif R[1, 1] > R[2, 2]:
+        s = 2.0 * np.sqrt(1.0 + R[1, 1] - R[0, 0] - R[2, 2])
+        q = [(R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s]
+    else:
+        s = 2.0 * np.sqrt(1.0 + R[2, 2] - R[0, 0] - R[1, 1])
+        q = [(R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s]
+    q = np.array(q) / np.linalg.norm(q)
+    return [float(x) for x in (q if q[0] >= 0 else -q)]
+
+
+def save_field_layout(path, tags, field_length=None, field_width=None):
+    """Write a field layout -- (id, R, t) triples, x_field = R x_tag + t in at_pose's tag frame, e.g.
+    FieldMapper's refined tags -- as the WPILib layout JSON load_field_layout reads: per tag "ID" and
+    "pose" with "translation" {x, y, z} and "rotation" {"quaternion" {W, X, Y, Z}} of the tag in
+    WPILib's tag frame (WPILIB_TAG_AXES undone; the same convention as load_field_layout, like it
+    unchecked against WPILib), tags by ascending id, and "field" {"length", "width"} when given.
+    Numbers are written with the digits that read back to the same float64, so load_field_layout
+    returns t bit for bit and R as the rotation of the printed quaternion, within a few units in
+    the last place of the R given.  Returns the path."""
+    out = []
+    for tid, R, t in sorted(load_field_layout(tags), key=lambda g: g[0]):
+        w, x, y, z = _rotation_quat(R @ WPILIB_TAG_AXES.T)
+        out.append({"ID": int(tid), "pose": {"translation": {"x": float(t[0]), "y": float(t[1]), "z": float(t[2])},
+                                             "rotation": {"quaternion": {"W": w, "X": x, "Y": y, "Z": z}}}})
+    data = {"tags": out}
+    if field_length is not None or field_width is not None:
+        data["field"] = {"length": float(field_length or 0.0), "width": float(field_width or 0.0)}
+    with open(path, "w") as f:
+        json.dump(data, f, indent=2)
+        f.write("\n")
+    return path
+
+
 def save_camera_calibration(calibration_dir, serial, cam, dist, rms, extra=None):
     """Write calibrationmatrix_<serial>.json as the reference's calibration nodes do and
     load_camera_calibration reads it: "matrix" 3 x 3, "disto" one row of (k1, k2, p1, p2, k3),
