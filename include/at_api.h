@@ -736,6 +736,86 @@ int at_rigcal_set_profiling(at_rigcal *c, int on);
 int at_rigcal_stats(const at_rigcal *c, uint64_t *out, int cap);
 void at_rigcal_destroy(at_rigcal *c);
 
+/* Rig track: the robot's field pose over a sliding window of instants linked by odometry.
+ *
+ * A fixed-lag smoother.  The window is the last `window` pushed instants, oldest dropped first,
+ * always one connected chain.  An instant holds, per camera, the rig pose's selection of layout
+ * tags (what at_rigcal_add stores), a time stamp (passed through) and the odometry since the
+ * previous instant: the robot now in the previous instant's robot frame, x_prev = R x_now + t, with
+ * standard deviations sigma_rot (radians) and sigma_trans (metres).  An instant in which no camera
+ * has a layout tag is stored too: its odometry alone holds it.
+ * Unknowns: x_field = R_k x_robot + t_k at every instant, parameters (w, dt) as the rig pose.  Cost:
+ * every selected corner's pixel residual / sigma_px (projected as the rig pose does; Pz <= 0 costs
+ * infinity), and for k >= 1, with E = R_m^T R_{k-1}^T R_k, the rotation residual
+ * 1/2 (E[7] - E[5], E[2] - E[6], E[3] - E[1]) / sigma_rot and the translation residual
+ * (R_{k-1}^T (t_k - t_{k-1}) - t_m) / sigma_trans.
+ * Start, a pure function of the window: an instant with tags starts from the rig pose over its
+ * stored tags; one without from its predecessor's start composed with its odometry; leading
+ * tagless instants backwards from the first instant that has a start.
+ * `iters` Levenberg-Marquardt iterations, lambda from 1e-3, / 10 (floor 1e-9) on an accepted step
+ * (the total cost fell and every Pz stayed positive), x 10 on a rejected one; the block-tridiagonal
+ * normal equations are solved by block Cholesky in ascending instants, and a pivot that is not
+ * positive is a rejected iteration.  cov is the inverse of the latest instant's last Schur block of
+ * the undamped system at the final state, order (w, t), not rescaled; cov_valid = 0 (and zeros)
+ * without a factor.
+ *
+ * at_rigtrack_create: AT_E_INVALID for a NULL, n_cams outside 1..AT_RIG_MAX_CAMS, a layout
+ * at_set_field_layout would refuse, max_hamming < 0, tag_size or sigma_px not positive and finite,
+ * an R that is no rotation, window outside 2..AT_RIGTRACK_MAX_WINDOW, iters outside 1..16.
+ * at_rigtrack_push: one instant, frames[c] as at_rigcal_add (at most AT_FIELD_MAX_TAGS tags per
+ * camera are kept).  odom = NULL: the first instant of a chain; with instants stored the window is
+ * emptied first (odometry was lost).  AT_E_INVALID for a NULL, a frame with n < 0 or n > 0 and a
+ * NULL array, an odom whose R is no rotation, whose t is not finite or whose sigmas are not positive
+ * and finite; nothing changes then.  Returns the window's count.
+ * at_rigtrack_solve: the solve on the GPU (kernels k_trk_*, on a stream of the tracker's own; one
+ * synchronisation, at the end).  at_rigtrack_solve_host: the same on the CPU, the kernels'
+ * arithmetic in the kernels' order: bit-equal records.  Neither changes what a later solve gives.
+ * Both AT_E_INVALID for an empty window or one in which no instant has a start.
+ * at_rigtrack_instants: per instant of the last solve, oldest first; returns the count, writes at
+ * most cap.  rms_px = 0 for n_tags = 0.
+ * at_rigtrack_stats, the last solve: [0] window size, [1] tags used, [2] accepted steps,
+ * [3] rejected steps, then the kernels' time in nanoseconds from HIP events while
+ * at_rigtrack_set_profiling is on (0 otherwise; a profiled solve records an event pair per launch):
+ * [4] all, [5] k_trk_start and k_trk_fill, [6] k_trk_accum, [7] k_trk_solve. */
+#define AT_RIGTRACK_MAX_WINDOW 64
+typedef struct {
+  at_camera cam;
+  at_rig_extrinsics extr;
+} at_rigtrack_camera;
+typedef struct {
+  double R[9]; double t[3];            /* x_prev = R x_now + t */
+  double sigma_rot, sigma_trans;
+} at_rigtrack_odom;
+typedef struct {
+  int32_t n, with_tags;                /* instants in the window, of them with a start of their own */
+  int32_t accepted, rejected;
+  double cost_before, cost_after;      /* the whole cost, sigmas applied */
+  double rms_before, rms_after;        /* pixels, over the corners */
+  double R[9]; double t[3];            /* the latest instant: x_field = R x_robot + t */
+  double cov[36];
+  double stamp;
+  int32_t cov_valid, pad;
+} at_rigtrack_result;
+typedef struct {
+  double R[9]; double t[3];
+  double stamp;
+  double rms_px;
+  int32_t n_tags, pad;
+} at_rigtrack_instant;
+typedef struct at_rigtrack at_rigtrack;
+int at_rigtrack_create(const at_rigtrack_camera *cams, int n_cams, const at_field_tag *tags, int n_tags,
+                       int max_hamming, double tag_size, double sigma_px, int window, int iters,
+                       at_rigtrack **out);
+int at_rigtrack_push(at_rigtrack *t, double stamp, const at_rigcal_frame *frames, const at_rigtrack_odom *odom);
+int at_rigtrack_count(const at_rigtrack *t);
+int at_rigtrack_clear(at_rigtrack *t);
+int at_rigtrack_solve(at_rigtrack *t, at_rigtrack_result *out);
+int at_rigtrack_solve_host(at_rigtrack *t, at_rigtrack_result *out);
+int at_rigtrack_instants(const at_rigtrack *t, at_rigtrack_instant *out, int cap);
+int at_rigtrack_set_profiling(at_rigtrack *t, int on);
+int at_rigtrack_stats(const at_rigtrack *t, uint64_t *out, int cap);
+void at_rigtrack_destroy(at_rigtrack *t);
+
 /* Camera calibration: the intrinsics and distortion of one camera from views of a tag board.
  *
  * A board is an at_field_tag array: each tag's pose in the board frame, any rigid arrangement.

@@ -14,6 +14,7 @@ from .detector import (AT_FMT_BGR8, AT_FMT_GRAY8, AT_FMT_YUYV, TAG_SIZE, TEST_CA
                        FieldPose, FieldPoseError, field_pose_host, robot_in_field,
                        AT_RIG_MAX_CAMS, RigPose, RigSolver, rig_pose_host,
                        AT_RIGCAL_MAX_INSTANTS, RigCalibration, RigCalibrator, RigCalInstant,
+                       AT_RIGTRACK_MAX_WINDOW, RigTrack, RigTracker, RigTrackInstant,
                        AT_CAMCAL_ALL, AT_CAMCAL_CX, AT_CAMCAL_CY, AT_CAMCAL_FX, AT_CAMCAL_FY, AT_CAMCAL_K1, AT_CAMCAL_K2,
                        AT_CAMCAL_K3, AT_CAMCAL_MAX_VIEWS, AT_CAMCAL_P1, AT_CAMCAL_P2, AT_CAMCAL_PINHOLE, CAMCAL_PARAMS,
                        CameraCalibration, CameraCalibrator, CameraCalView,
@@ -28,6 +29,7 @@ __all__ = ["GpuDetector", "CameraMatrix", "DistCoeffs", "Detection", "Pose", "Ta
            "FieldPose", "FieldPoseError", "field_pose_host", "robot_in_field",
            "AT_RIG_MAX_CAMS", "RigPose", "RigSolver", "rig_pose_host",
            "AT_RIGCAL_MAX_INSTANTS", "RigCalibration", "RigCalibrator", "RigCalInstant",
+           "AT_RIGTRACK_MAX_WINDOW", "RigTrack", "RigTracker", "RigTrackInstant",
            "AT_CAMCAL_MAX_VIEWS", "AT_CAMCAL_FX", "AT_CAMCAL_FY", "AT_CAMCAL_CX", "AT_CAMCAL_CY", "AT_CAMCAL_K1",
            "AT_CAMCAL_K2", "AT_CAMCAL_P1", "AT_CAMCAL_P2", "AT_CAMCAL_K3", "AT_CAMCAL_PINHOLE", "AT_CAMCAL_ALL",
            "CAMCAL_PARAMS", "CameraCalibration", "CameraCalibrator", "CameraCalView",

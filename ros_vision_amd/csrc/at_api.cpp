@@ -28,6 +28,7 @@
 #include "at_rigcal.h"
 #include "at_fieldmap.h"
 #include "at_camcal.h"
+#include "at_rigtrack.h"
 
 namespace at {
 hipError_t launch_tap_sizes(const uint8_t* thr, const uint32_t* par, const uint32_t* size, uint32_t* out, int Wd,
@@ -61,6 +62,7 @@ hipError_t launch_rig(const RigBufs& rb, int ninstants, hipStream_t st);
 hipError_t launch_rigcal(const CalBufs& b, hipStream_t st);
 hipError_t launch_camcal(const CcBufs& b, hipStream_t st);
 hipError_t launch_fieldmap(const FmBufs& b, hipStream_t st);
+hipError_t launch_rigtrack(const TrkBufs& b, const TrkTodo& todo, int iters, hipStream_t st, hipEvent_t* ev);
 
 struct CodeEntry {
   int id;
@@ -2788,6 +2790,166 @@ int at_fieldmap_solve(at_fieldmap* m, at_fieldmap_result* out) {
   fm_finish(m, b, *g->h_ctl, g->h_start, seen.data(), g->h_tag[w], g->h_cov, g->h_pose[w], g->h_viewcost, g->h_ntags,
             out);
   m->ns = ns;
+  return AT_OK;
+}
+
+// ---- rig track -------------------------------------------------------------------
+// The device side of an at_rigtrack (at_rigtrack.cpp holds the rest), as CalGpu: a stream and
+// events of its own, the layout, the ring of stored instants and their own starts in HBM (a slot
+// is uploaded, and its start computed, once per stored instant), the solve's buffers for a full
+// window, and pinned host memory for what comes back.  Everything is sized by the window at the
+// first solve.
+namespace at {
+constexpr int kTrkEvents = 3 + 2 * (kTrkMaxIters + 1);
+struct TrkGpu {
+  int device;
+  hipStream_t st;
+  hipEvent_t ev[kTrkEvents];
+  bool ready;
+  std::vector<void*> dev, host;
+  TrkBufs b;  // device pointers
+  CalPose* h_pose[2];
+  double *h_instpx, *h_cov;
+  int32_t* h_own_nt;
+  TrkCtl* h_ctl;
+};
+}  // namespace at
+
+static void trkgpu_free(TrkGpu* g) {
+  if (!g) return;
+  (void)hipSetDevice(g->device);
+  if (g->st) (void)hipStreamSynchronize(g->st);
+  for (void* p : g->dev) (void)hipFree(p);
+  for (void* p : g->host) (void)hipHostFree(p);
+  for (hipEvent_t e : g->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (g->st) (void)hipStreamDestroy(g->st);
+  delete g;
+}
+
+static int trkgpu_reserve(at_rigtrack* t, TrkGpu* g) {
+  bool ok = true;
+  auto dmal = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (!ok || hipMalloc(&p, bytes) != hipSuccess) {
+      ok = false;
+      return nullptr;
+    }
+    g->dev.push_back(p);
+    return p;
+  };
+  auto hmal = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (!ok || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+      ok = false;
+      return nullptr;
+    }
+    g->host.push_back(p);
+    return p;
+  };
+  TrkBufs& b = g->b;
+  memset(&b, 0, sizeof(b));
+  const size_t W = (size_t)t->window, nc = (size_t)t->n_cams;
+  b.obs = (const CalCamObs*)dmal(W * nc * sizeof(CalCamObs));
+  b.odom = (const TrkOdom*)dmal(W * sizeof(TrkOdom));
+  b.rec = (RigRecord*)dmal(W * sizeof(RigRecord));
+  b.own = (CalPose*)dmal(W * sizeof(CalPose));
+  b.own_nt = (int32_t*)dmal(W * sizeof(int32_t));
+  for (int q = 0; q < 2; q++) {
+    b.pose[q] = (CalPose*)dmal(W * sizeof(CalPose));
+    b.sums[q] = (double*)dmal(W * kTrkSums * sizeof(double));
+    g->h_pose[q] = (CalPose*)hmal(W * sizeof(CalPose));
+  }
+  b.instpx = (double*)dmal(W * sizeof(double));
+  b.cov = (double*)dmal(36 * sizeof(double));
+  b.ctl = (TrkCtl*)dmal(sizeof(TrkCtl));
+  b.lay.lut = (const int16_t*)dmal(kFpMaxIds * sizeof(int16_t));
+  b.lay.tags = (const FpTag*)dmal(t->tags.size() * sizeof(FpTag));
+  b.lay.max_hamming = t->max_hamming;
+  g->h_instpx = (double*)hmal(W * sizeof(double));
+  g->h_cov = (double*)hmal(36 * sizeof(double));
+  g->h_own_nt = (int32_t*)hmal(W * sizeof(int32_t));
+  g->h_ctl = (TrkCtl*)hmal(sizeof(TrkCtl));
+  if (!ok) return AT_E_NOMEM;
+  if (hipMemcpy((void*)b.lay.lut, t->lut.data(), kFpMaxIds * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((void*)b.lay.tags, t->tags.data(), t->tags.size() * sizeof(FpTag), hipMemcpyHostToDevice) !=
+          hipSuccess ||
+      hipMemset(b.own_nt, 0, W * sizeof(int32_t)) != hipSuccess)
+    return AT_E_HIP;
+  t->dev_stale.assign(W, 1);
+  g->ready = true;
+  return AT_OK;
+}
+
+int at_rigtrack_solve(at_rigtrack* t, at_rigtrack_result* out) {
+  if (!t || !out || t->n < 1) return AT_E_INVALID;
+  {  // (no kernel is launched for a window without a tag)
+    bool any = false;
+    for (int k = 0; k < t->n && !any; k++)
+      for (int c = 0; c < t->n_cams && !any; c++)
+        any = t->obs[(size_t)((t->head + k) % t->window) * t->n_cams + c].m > 0;
+    if (!any) return AT_E_INVALID;
+  }
+  TrkGpu* g = t->gpu;
+  if (!g) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return AT_E_HIP;
+    g = new TrkGpu();
+    g->device = dev;
+    bool ok = hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; i < kTrkEvents && ok; i++) ok = hipEventCreateWithFlags(&g->ev[i], kTimingEventFlags) == hipSuccess;
+    if (!ok) {
+      trkgpu_free(g);
+      return AT_E_HIP;
+    }
+    t->gpu = g;
+    t->gpu_free = trkgpu_free;
+  }
+  if (hipSetDevice(g->device) != hipSuccess) return AT_E_HIP;
+  if (!g->ready) {
+    const int rc = trkgpu_reserve(t, g);
+    if (rc != AT_OK) return rc;
+  }
+  TrkBufs b = g->b;
+  const FpLayout lay = b.lay;
+  trk_fill_bufs(*t, &b);
+  b.lay = lay;
+  const size_t W = (size_t)t->window, N = (size_t)t->n, nc = (size_t)t->n_cams;
+  TrkTodo todo;
+  memset(&todo, 0, sizeof(todo));
+  for (int k = 0; k < t->n; k++) {
+    const int s = b.slot(k);
+    if (!t->dev_stale[(size_t)s]) continue;
+    HIPCHK(hipMemcpyAsync((void*)(b.obs + (size_t)s * nc), t->obs.data() + (size_t)s * nc, nc * sizeof(CalCamObs),
+                          hipMemcpyHostToDevice, g->st));
+    HIPCHK(hipMemcpyAsync((void*)(b.odom + s), t->odom.data() + s, sizeof(TrkOdom), hipMemcpyHostToDevice, g->st));
+    todo.slot[todo.n++] = (uint8_t)s;
+  }
+  const int n_ev = 3 + 2 * (t->iters + 1);
+  HIPCHK(launch_rigtrack(b, todo, t->iters, g->st, t->profiling ? g->ev : nullptr));
+  // (a slot counts as held by the device only now: a failure above leaves it to the next solve)
+  for (int i = 0; i < todo.n; i++) t->dev_stale[todo.slot[i]] = 0;
+  HIPCHK(hipMemcpyAsync(g->h_ctl, b.ctl, sizeof(TrkCtl), hipMemcpyDeviceToHost, g->st));
+  for (int q = 0; q < 2; q++)
+    HIPCHK(hipMemcpyAsync(g->h_pose[q], b.pose[q], N * sizeof(CalPose), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(g->h_cov, b.cov, 36 * sizeof(double), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(g->h_instpx, b.instpx, N * sizeof(double), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipMemcpyAsync(g->h_own_nt, b.own_nt, W * sizeof(int32_t), hipMemcpyDeviceToHost, g->st));
+  HIPCHK(hipStreamSynchronize(g->st));
+  uint64_t ns[4] = {0, 0, 0, 0};
+  if (t->profiling) {
+    for (int i = 0; i + 1 < n_ev; i++) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, g->ev[i], g->ev[i + 1]));
+      const uint64_t v = (uint64_t)((double)ms * 1e6);
+      ns[0] += v;
+      ns[i < 2 ? 1 : (i & 1) ? 3 : 2] += v;
+    }
+  }
+  if (!g->h_ctl->any) return AT_E_INVALID;
+  const int w = g->h_ctl->which & 1;
+  trk_finish(t, *g->h_ctl, g->h_pose[w], g->h_cov, g->h_instpx, g->h_own_nt, out);
+  for (int i = 0; i < 4; i++) t->ns[i] = ns[i];
   return AT_OK;
 }
 

@@ -32,6 +32,7 @@
 #include "at_rigcal.h"
 #include "at_fieldmap.h"
 #include "at_camcal.h"
+#include "at_rigtrack.h"
 
 
 namespace at {
@@ -6519,6 +6520,68 @@ hipError_t launch_fieldmap(const FmBufs& b, hipStream_t st) {
     hipLaunchKernelGGL(k_fm_decide, one, team, 0, st, b, 1);
   }
   hipLaunchKernelGGL(k_fm_back, per_view, wave, 0, st, b, 0);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Rig track (at_rigtrack_solve): the robot's pose over a window of N <= 64 instants linked by
+// odometry; the algorithm is at_rigtrack.h's, which at_rigtrack_solve_host runs with one thread.
+// k_trk_start: one workgroup per instant whose own start is still to be computed (TrkTodo), one
+// wave per camera, rig_solve_instant as k_cal_start.  k_trk_fill: one thread walks the chain.
+// k_trk_accum: one workgroup per instant, one wave per camera, one lane per corner slot; the 28
+// vision sums through the halving butterfly into the camera's LDS row, thread 0 forms the odometry
+// rows of the factor to the predecessor meanwhile, and after one barrier the 149 sums (the
+// cameras added in order, the factor's products) are spread over the threads.  k_trk_solve: one
+// workgroup of one wave: the lanes read the instants' costs of what k_trk_accum just evaluated side
+// by side into LDS, thread 0 adds them up in order and takes the decision (TrkCtl::which in HBM),
+// then the blocks are assembled into LDS, 42 entries per
+// instant over the lanes, and factored along the chain: per instant six lanes substitute the rows
+// of B_k, 36 lanes form D_k - B_k B_k^T, and the 6 x 6 factor runs column by column with a lane per
+// row -- eight barriers of one wave per instant; thread 0 substitutes forwards and back, and the
+// lanes write the candidate poses.  A solve is 2 + 2 (iters + 1) launches (one less when every own
+// start is known), with no host round trip in between.  Branches around barriers depend on TrkCtl, on
+// own_nt of the workgroup's instant and on the sizes only: uniform over a workgroup.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * kRigMaxCams) void k_trk_start(TrkBufs b, TrkTodo todo) {
+  __shared__ RigShared sh;
+  const int i = (int)blockIdx.x;
+  if (i >= todo.n) return;
+  const int s = (int)todo.slot[i];
+  if (s >= b.W) return;
+  trk_start(cal_team(), sh, b, s);
+}
+__global__ __launch_bounds__(64) void k_trk_fill(TrkBufs b) { trk_fill(cal_team(), b); }
+__global__ __launch_bounds__(64 * kRigMaxCams) void k_trk_accum(TrkBufs b, int cand) {
+  __shared__ TrkShared sh;
+  const int k = (int)blockIdx.x;
+  if (k >= b.N) return;
+  trk_accum(cal_team(), sh, b, k, cand != 0);
+}
+__global__ __launch_bounds__(64) void k_trk_solve(TrkBufs b, int first, int final) {
+  __shared__ TrkSolveShared sh;
+  trk_solve(cal_team(), sh, b, first != 0, final != 0);
+}
+// the whole solve, in order on st.  ev (may be NULL): an event before every launch and one after the
+// last, 3 + 2 (iters + 1) of them (the first two coincide when todo is empty)
+hipError_t launch_rigtrack(const TrkBufs& b, const TrkTodo& todo, int iters, hipStream_t st, hipEvent_t* ev) {
+  if (b.N < 1 || b.N > b.W || b.W > kTrkMaxWindow || todo.n < 0 || todo.n > b.W) return hipErrorInvalidValue;
+  const dim3 per_instant(b.N), team(64 * b.n_cams), one(1), wave(64);
+  int e = 0;
+  auto mark = [&]() {
+    if (ev) (void)hipEventRecord(ev[e], st);
+    e++;
+  };
+  mark();
+  if (todo.n > 0) hipLaunchKernelGGL(k_trk_start, dim3(todo.n), team, 0, st, b, todo);
+  mark();
+  hipLaunchKernelGGL(k_trk_fill, one, wave, 0, st, b);
+  for (int it = 0; it <= iters; it++) {
+    mark();
+    hipLaunchKernelGGL(k_trk_accum, per_instant, team, 0, st, b, it > 0);
+    mark();
+    hipLaunchKernelGGL(k_trk_solve, one, wave, 0, st, b, it == 0, it == iters);
+  }
+  mark();
   return hipGetLastError();
 }
 

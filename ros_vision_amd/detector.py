@@ -48,6 +48,9 @@ EXPORTS = [
     "at_rig_create", "at_rig_solve", "at_rig_stats", "at_rig_destroy", "at_rig_pose_host",
     "at_rigcal_create", "at_rigcal_add", "at_rigcal_count", "at_rigcal_clear", "at_rigcal_solve",
     "at_rigcal_solve_host", "at_rigcal_instants", "at_rigcal_set_profiling", "at_rigcal_stats", "at_rigcal_destroy",
+    "at_rigtrack_create", "at_rigtrack_push", "at_rigtrack_count", "at_rigtrack_clear", "at_rigtrack_solve",
+    "at_rigtrack_solve_host", "at_rigtrack_instants", "at_rigtrack_set_profiling", "at_rigtrack_stats",
+    "at_rigtrack_destroy",
     "at_camcal_create", "at_camcal_add", "at_camcal_count", "at_camcal_clear", "at_camcal_solve",
     "at_camcal_solve_host", "at_camcal_views", "at_camcal_set_profiling", "at_camcal_stats", "at_camcal_destroy",
     "at_fieldmap_create", "at_fieldmap_add", "at_fieldmap_count", "at_fieldmap_clear", "at_fieldmap_solve",
@@ -55,6 +58,7 @@ EXPORTS = [
     "at_fieldmap_stats", "at_fieldmap_destroy",
 ]
 AT_RIGCAL_MAX_INSTANTS = 4096
+AT_RIGTRACK_MAX_WINDOW = 64
 AT_CAMCAL_MAX_VIEWS = 4096
 AT_FIELDMAP_MAX_TAGS = 32
 AT_FIELDMAP_MAX_VIEWS = 4096
@@ -150,6 +154,26 @@ class AtRigcalResult(C.Structure):
 class AtRigcalInstant(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("rms_px", C.c_double), ("n_tags", C.c_int32),
                 ("used", C.c_int32)]
+
+
+class AtRigtrackCamera(C.Structure):
+    _fields_ = [("cam", AtCamera), ("extr", AtRigExtrinsics)]
+
+
+class AtRigtrackOdom(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("sigma_rot", C.c_double), ("sigma_trans", C.c_double)]
+
+
+class AtRigtrackResult(C.Structure):
+    _fields_ = [("n", C.c_int32), ("with_tags", C.c_int32), ("accepted", C.c_int32), ("rejected", C.c_int32),
+                ("cost_before", C.c_double), ("cost_after", C.c_double), ("rms_before", C.c_double),
+                ("rms_after", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3), ("cov", C.c_double * 36),
+                ("stamp", C.c_double), ("cov_valid", C.c_int32), ("pad", C.c_int32)]
+
+
+class AtRigtrackInstant(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("stamp", C.c_double), ("rms_px", C.c_double),
+                ("n_tags", C.c_int32), ("pad", C.c_int32)]
 
 
 class AtCamcalConfig(C.Structure):
@@ -285,6 +309,36 @@ class RigCalInstant:
     rms_px: float
     n_tags: int
     used: bool
+
+
+@dataclass
+class RigTrack:
+    """at_rigtrack_result: the latest instant's smoothed robot pose x_field = R x_robot + t, its
+    6 x 6 covariance in (w, t) order -- w a small turn in the robot frame, t in the field frame --
+    and what the solve over the window did."""
+    R: np.ndarray      # [3, 3]
+    t: np.ndarray      # [3]
+    cov: np.ndarray    # [6, 6]; zeros unless cov_valid
+    cov_valid: bool
+    stamp: float
+    n: int
+    with_tags: int
+    accepted: int
+    rejected: int
+    cost_before: float
+    cost_after: float
+    rms_before: float
+    rms_after: float
+
+
+@dataclass
+class RigTrackInstant:
+    """at_rigtrack_instant: an instant's final robot pose (n_tags 0: held by odometry alone)."""
+    R: np.ndarray
+    t: np.ndarray
+    stamp: float
+    rms_px: float
+    n_tags: int
 
 
 @dataclass
@@ -544,6 +598,19 @@ def load_library(path: str = LIB_PATH):
         L.at_rigcal_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
         L.at_rigcal_destroy.argtypes = [C.c_void_p]
         L.at_rigcal_destroy.restype = None
+    if hasattr(L, "at_rigtrack_solve"):  # (A/B builds of older sources lack the rig track)
+        L.at_rigtrack_create.argtypes = [C.POINTER(AtRigtrackCamera), C.c_int, C.POINTER(AtFieldTag), C.c_int, C.c_int,
+                                         C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.at_rigtrack_push.argtypes = [C.c_void_p, C.c_double, C.POINTER(AtRigcalFrame), C.POINTER(AtRigtrackOdom)]
+        for name in ("at_rigtrack_count", "at_rigtrack_clear"):
+            getattr(L, name).argtypes = [C.c_void_p]
+        for name in ("at_rigtrack_solve", "at_rigtrack_solve_host"):
+            getattr(L, name).argtypes = [C.c_void_p, C.POINTER(AtRigtrackResult)]
+        L.at_rigtrack_instants.argtypes = [C.c_void_p, C.POINTER(AtRigtrackInstant), C.c_int]
+        L.at_rigtrack_set_profiling.argtypes = [C.c_void_p, C.c_int]
+        L.at_rigtrack_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.at_rigtrack_destroy.argtypes = [C.c_void_p]
+        L.at_rigtrack_destroy.restype = None
     if hasattr(L, "at_camcal_solve"):  # (A/B builds of older sources lack the camera calibration)
         L.at_camcal_create.argtypes = [C.POINTER(AtCamcalConfig), C.POINTER(AtFieldTag), C.c_int, C.c_int, C.c_double,
                                        C.POINTER(C.c_void_p)]
@@ -1210,6 +1277,116 @@ class RigCalibrator:
     def close(self):
         if getattr(self, "_h", None):
             load_library().at_rigcal_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+# ---- rig track (k_trk_*) -----------------------------------------------------------
+class RigTracker:
+    """at_rigtrack: the robot's pose over a sliding window of instants linked by odometry (a
+    fixed-lag smoother).  `cameras` is one (camera_matrix, (R, t)) per camera -- its CameraMatrix and
+    its extrinsics x_robot = R x_cam + t (None: identity); `layout` the (id, R, t) triples
+    set_field_layout takes; `sigma_px` the standard deviation of a corner in pixels; `window` the
+    instants kept (2..64), `iters` the Levenberg-Marquardt iterations of a solve (1..16).  Raises
+    FieldPoseError for arguments the library refuses."""
+
+    def __init__(self, cameras, layout, max_hamming=0, tag_size=TAG_SIZE, sigma_px=0.5, window=32, iters=6):
+        L = load_library()
+        cameras = list(cameras)
+        self.n_cams = n = len(cameras)
+        arr = (AtRigtrackCamera * max(1, n))()
+        ext, _n = _rig_extrinsics([c[1] for c in cameras], n)
+        for i, (cam, _e) in enumerate(cameras):
+            arr[i].cam = AtCamera(fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy)
+            arr[i].extr = ext[i]
+        tarr, nt = _field_tags(layout)
+        h = C.c_void_p()
+        self._h = None
+        rc = L.at_rigtrack_create(arr, n, tarr, nt, int(max_hamming), float(tag_size), float(sigma_px), int(window),
+                                  int(iters), C.byref(h))
+        if rc < 0:
+            raise FieldPoseError("at_rigtrack_create", rc)
+        self._h = h
+
+    _frames = RigCalibrator._frames
+
+    def push(self, per_camera_results, odometry=None, stamp=0.0):
+        """at_rigtrack_push: one instant, per camera (detections, poses) of its frame (None or empty:
+        the camera saw nothing; an instant without any tag is stored too).  `odometry` is
+        (R, t, sigma_rot, sigma_trans): the robot now in the previous instant's robot frame,
+        x_prev = R x_now + t; None starts a new chain (the window is emptied first).  Returns the
+        window's count."""
+        arr, _keep = self._frames(per_camera_results)
+        od = None
+        if odometry is not None:
+            R, t, sigma_rot, sigma_trans = odometry
+            od = AtRigtrackOdom(sigma_rot=float(sigma_rot), sigma_trans=float(sigma_trans))
+            od.R[:] = [float(x) for x in np.asarray(R, np.float64).reshape(9)]
+            od.t[:] = [float(x) for x in np.asarray(t, np.float64).reshape(3)]
+        rc = load_library().at_rigtrack_push(self._h, float(stamp), arr, C.byref(od) if od is not None else None)
+        if rc < 0:
+            raise FieldPoseError("at_rigtrack_push", rc)
+        return int(rc)
+
+    def __len__(self):
+        return int(load_library().at_rigtrack_count(self._h))
+
+    def clear(self):
+        _check(load_library().at_rigtrack_clear(self._h), "at_rigtrack_clear")
+
+    def _solve(self, name):
+        out = AtRigtrackResult()
+        rc = getattr(load_library(), name)(self._h, C.byref(out))
+        if rc < 0:
+            raise FieldPoseError(name, rc)
+        self.record = out
+        return RigTrack(R=np.array(list(out.R)).reshape(3, 3), t=np.array(list(out.t)),
+                        cov=np.array(list(out.cov)).reshape(6, 6), cov_valid=bool(out.cov_valid), stamp=out.stamp,
+                        n=out.n, with_tags=out.with_tags, accepted=out.accepted, rejected=out.rejected,
+                        cost_before=out.cost_before, cost_after=out.cost_after, rms_before=out.rms_before,
+                        rms_after=out.rms_after)
+
+    def solve(self):
+        """at_rigtrack_solve: the solve on the GPU (the current device), on the tracker's own stream."""
+        return self._solve("at_rigtrack_solve")
+
+    def solve_host(self):
+        """at_rigtrack_solve_host: the same solve on the CPU, bit-equal records."""
+        return self._solve("at_rigtrack_solve_host")
+
+    def instants(self):
+        """at_rigtrack_instants: one RigTrackInstant per instant of the last solve, oldest first."""
+        L = load_library()
+        n = _check(L.at_rigtrack_instants(self._h, None, 0), "at_rigtrack_instants")
+        buf = (AtRigtrackInstant * max(1, n))()
+        n = _check(L.at_rigtrack_instants(self._h, buf, n), "at_rigtrack_instants")
+        return [RigTrackInstant(R=np.array(list(b.R)).reshape(3, 3), t=np.array(list(b.t)), stamp=b.stamp,
+                                rms_px=b.rms_px, n_tags=b.n_tags) for b in buf[:n]]
+
+    def instant_records(self):
+        """The at_rigtrack_instant records of the last solve as bytes (for equality checks)."""
+        L = load_library()
+        n = _check(L.at_rigtrack_instants(self._h, None, 0), "at_rigtrack_instants")
+        buf = (AtRigtrackInstant * max(1, n))()
+        n = _check(L.at_rigtrack_instants(self._h, buf, n), "at_rigtrack_instants")
+        return bytes(buf)[:n * C.sizeof(AtRigtrackInstant)]
+
+    def set_profiling(self, on=True):
+        _check(load_library().at_rigtrack_set_profiling(self._h, int(bool(on))), "at_rigtrack_set_profiling")
+
+    def stats(self):
+        """at_rigtrack_stats of the last solve."""
+        buf = (C.c_uint64 * 8)()
+        n = _check(load_library().at_rigtrack_stats(self._h, buf, len(buf)), "at_rigtrack_stats")
+        names = ("window", "tags_used", "accepted_steps", "rejected_steps", "kernel_ns", "start_ns", "accum_ns",
+                 "solve_ns")
+        return {k: int(v) for k, v in zip(names[:n], buf)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().at_rigtrack_destroy(self._h)
             self._h = None
 
     def __del__(self):

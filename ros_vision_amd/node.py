@@ -31,7 +31,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .detector import (AT_FMT_BGR8, AT_FMT_GRAY8, AT_FMT_YUYV, TAG_SIZE, CameraMatrix, DistCoeffs, GpuDetector,
-                       RigSolver, robot_in_field, tag_detections)
+                       FieldPoseError, RigSolver, robot_in_field, tag_detections)
 
 PARAMETER_DEFAULTS = {
     "topic_name": "camera/image_raw",
@@ -562,9 +562,12 @@ class RigPoseFuser:
     x_field = R x_robot + t, cov 6 x 6 in (w, t) order (RigPose) -- on
     <publish_pose_to_topic>/rig of the first node; an instant without a layout tag sends nothing.
     With a `calibrator` (RigCalibrator over the same cameras, in the nodes' order) every fused
-    instant is also added to it, from the nodes' collected detections and poses."""
+    instant is also added to it, from the nodes' collected detections and poses.
+    With a `tracker` (RigTracker over the same cameras, in the nodes' order) every instant is pushed
+    to it -- one without a tag too, which its odometry holds -- and the smoothed latest (R, t, cov)
+    (RigTrack) goes out on <publish_pose_to_topic>/rig/tracked."""
 
-    def __init__(self, camera_nodes, field_layout, max_hamming=0, publishers=None, calibrator=None):
+    def __init__(self, camera_nodes, field_layout, max_hamming=0, publishers=None, calibrator=None, tracker=None):
         self.nodes = list(camera_nodes)
         self.field_layout = load_field_layout(field_layout)
         self.solver = RigSolver([n.detector for n in self.nodes],
@@ -573,12 +576,17 @@ class RigPoseFuser:
         self.publishers = publishers if publishers is not None else self.nodes[0].publishers
         self.rig_pose_topic = self.nodes[0].pose_topic + "/rig"
         self.calibrator = calibrator
+        self.tracker = tracker
+        self.tracked_pose_topic = self.rig_pose_topic + "/tracked"
+        self.tracked = None
 
     def close(self):
         self.solver.close()
 
-    def publish(self):
-        """The RigPose of the instant the nodes last saw (published when it has a tag)."""
+    def publish(self, odometry=None, stamp_s=0.0):
+        """The RigPose of the instant the nodes last saw (published when it has a tag).  With a
+        tracker: `odometry` is RigTracker.push's (None: a new chain), `stamp_s` the instant's time;
+        the tracked pose is kept in self.tracked (None while the window has no tag)."""
         pose = self.solver.solve()[0]
         if pose.n_tags:
             fn = self.publishers.get(self.rig_pose_topic)
@@ -586,4 +594,13 @@ class RigPoseFuser:
                 fn((pose.R, pose.t, pose.cov))
         if self.calibrator is not None:
             self.calibrator.add([(n.detector.detections(0), n.detector.poses(0)) for n in self.nodes])
+        if self.tracker is not None:
+            self.tracker.push([(n.detector.detections(0), n.detector.poses(0)) for n in self.nodes], odometry, stamp_s)
+            try:
+                self.tracked = self.tracker.solve()
+            except FieldPoseError:  # (no tag anywhere in the window yet)
+                self.tracked = None
+            fn = self.publishers.get(self.tracked_pose_topic)
+            if self.tracked is not None and fn is not None:
+                fn((self.tracked.R, self.tracked.t, self.tracked.cov))
         return pose
