@@ -602,6 +602,42 @@ int at_field_pose_host(const at_detection *dets, const at_pose *poses, int n, co
 int at_robot_in_field(const at_field_pose *fp, const double *extr_R, const double *extr_t, double *R_out, double *t_out);
 int at_field_stats(at_detector *d, uint64_t *out, int cap);
 
+/* Ideal corners: the lens distortion undone before every pose solve (opt-in, off by default).
+ *
+ * The pose solves project through a pinhole, which is exact against *ideal* pixels: the raw ones
+ * mapped through the inverse of the forward model (k1, k2, p1, p2, k3 of at_camera, as
+ * at_camcal solves them).  With the mode on, the head of the pose stage maps each candidate's
+ * four corners (eight Newton steps with the analytic Jacobian, no early exit), recomputes H from
+ * them (homography_compute2's elimination) and c as the image of (0, 0); the tag pose, the field
+ * pose and the rig pose (per member; members with the mode on and off may be mixed) are computed
+ * from those.  No launch is added.  at_detections, at_collect, the annotated image, the preview
+ * and the camera calibration stay on raw corners.
+ *
+ * A pixel is not invertible when the Jacobian's determinant is not > 0 at an iterate or at the
+ * result (the model folds over: lenses with a large negative k3, near the image corners), or the
+ * result's forward image is not within 1e-6 px of it on each axis; NaN and infinity are not.  A
+ * detection with such a corner has an ideal record that is its raw record with id = -1: the
+ * field, rig, calibration and mapping selections pass it over; its own at_pose comes from its raw
+ * corners.  With all five coefficients zero the ideal record is a copy of the raw one.
+ *
+ * at_set_undistort: from the next enqueued batch; AT_E_INVALID for a NULL detector, a batch not
+ * yet collected, at_config.tag_size not positive.
+ * at_ideal_detections: like at_detections (same order and count), with H, c, p ideal and id = -1
+ * where not invertible; AT_E_INVALID when the last batch ran with the mode off.
+ * at_ideal_detections_host: the CPU twin on at_detections' records, bit-equal; returns n.
+ * at_undistort_points: n pixels (u, v pairs) through the same inverse on the detector's stream
+ * (k_und_points; for pixels that are no tag corners, such as a game piece's box centre); ok[i] = 0
+ * and out = the raw pixel where pixel i is not invertible.  Needs no mode; returns n.
+ * at_undistort_points_host: the CPU twin, bit-equal.
+ * at_undistort_stats, the last collected batch: [0] detections made ideal, [1] detections not
+ * invertible (both 0 with the mode off). */
+int at_set_undistort(at_detector *d, int on);
+int at_ideal_detections(at_detector *d, int frame, at_detection *out, int cap);
+int at_ideal_detections_host(const at_camera *cam, const at_detection *dets, int n, at_detection *out);
+int at_undistort_points(at_detector *d, const double *xy, int n, double *out_xy, uint8_t *ok);
+int at_undistort_points_host(const at_camera *cam, const double *xy, int n, double *out_xy, uint8_t *ok);
+int at_undistort_stats(at_detector *d, uint64_t *out, int cap);
+
 /* Rig pose: one robot pose per instant from the layout tags of every camera, with its covariance.
  *
  * A rig is 1..AT_RIG_MAX_CAMS detectors of one process on one device, each with its own

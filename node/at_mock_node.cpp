@@ -20,7 +20,7 @@
 //        [--measurement-csv PATH] [--proto-out P] [--image-out I] [--device K] [--time N]
 //        [--mjpg-color] [--mjpg-device-entropy] [--jpeg-out DIR] [--jpeg-quality Q]
 //        [--preview-out DIR --preview-scale N [--preview-quality Q] [--preview-max-bytes B]]
-//        [--field-layout FILE [--field-max-hamming M]]
+//        [--field-layout FILE [--field-max-hamming M]] [--undistort]
 //   As the reference node (apriltags_cuda_detector.cu:137-193): the frame size, the
 //   intrinsics and the extrinsics come from the camera serial's records in the
 //   vision_config_data share directory, found through $AMENT_PREFIX_PATH
@@ -35,6 +35,9 @@
 //   (x_field = R x_tag + t; DetectorCore::set_field_layout).  Every frame's line gains "field":
 //   the camera pose from all its layout tags (n_tags, ids, R, t, rms_px, steps) and, when there is
 //   one, "robot_R" / "robot_t", the robot's pose in the field.
+//   --undistort: the tag poses and the field pose from ideal corners, the calibration's lens
+//   distortion undone on the GPU (DetectorCore::set_undistort); the first line gains
+//   "undistort":true.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -101,11 +104,11 @@ int main(int argc, char** argv) {
   int field_max_hamming = 0;
   int preview_scale = 0, preview_quality = 50;
   long long preview_max_bytes = 0;
-  bool mjpg_color = false, mjpg_device_entropy = false;
+  bool mjpg_color = false, mjpg_device_entropy = false, undistort = false;
   for (int i = 1; i < argc; i += 2) {
     const std::string k = argv[i];
-    if (k == "--mjpg-color" || k == "--mjpg-device-entropy") {  // (the options without a value)
-      (k == "--mjpg-color" ? mjpg_color : mjpg_device_entropy) = true;
+    if (k == "--mjpg-color" || k == "--mjpg-device-entropy" || k == "--undistort") {  // (the options without a value)
+      (k == "--mjpg-color" ? mjpg_color : k == "--undistort" ? undistort : mjpg_device_entropy) = true;
       i -= 1;
       continue;
     }
@@ -193,8 +196,9 @@ int main(int argc, char** argv) {
   const bool sched_ok = at_node::apply_cpu_pinning_and_scheduling(prm.pin_to_core, prm.priority, &sched_log);
   std::fprintf(stderr, "%s", sched_log.c_str());
   std::printf("{\"width\":%d,\"height\":%d,\"fx\":%.17g,\"location\":\"%s\",\"scheduling_applied\":%s,"
-              "\"networktables\":\"%s\"}\n",
-              W, H, nc.cam.fx, location.c_str(), sched_ok ? "true" : "false", nc.networktables.table_address.c_str());
+              "\"networktables\":\"%s\"%s}\n",
+              W, H, nc.cam.fx, location.c_str(), sched_ok ? "true" : "false", nc.networktables.table_address.c_str(),
+              undistort ? ",\"undistort\":true" : "");
   Sink sink;
   try {
     at_node::DetectorCore core(prm, nc, device);
@@ -223,6 +227,7 @@ int main(int argc, char** argv) {
       }
       core.set_field_layout(tags, field_max_hamming);
     }
+    if (undistort) core.set_undistort(true);
     at_node::FrameOutputs out;
     at_node::ImageBuffer image;
     auto run = [&](int f, double stamp) {

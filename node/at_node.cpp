@@ -588,6 +588,12 @@ void DetectorCore::set_field_layout(const std::vector<at_field_tag>& tags, int m
   field_layout_ = !tags.empty();
 }
 
+void DetectorCore::set_undistort(bool on) {
+  const int rc = at_set_undistort(det_, on ? 1 : 0);
+  if (rc != AT_OK) throw std::runtime_error(std::string("set_undistort: ") + at_strerror(rc));
+  undistort_ = on;
+}
+
 bool load_field_layout(const std::string& path, std::vector<at_field_tag>* tags, std::string* err) {
   tags->clear();
   std::ifstream in(path);

@@ -287,6 +287,11 @@ class DetectorCore {
   // and the robot's field pose (at_robot_in_field with the node's extrinsics) goes to
   // publish_field_pose on field_pose_topic().
   void set_field_layout(const std::vector<at_field_tag>& tags, int max_hamming = 0);
+  // set_undistort(on): the tag poses and the field pose from ideal corners -- the lens distortion
+  // of the calibration undone on the GPU (at_set_undistort); the detections, the outlined image
+  // and the preview stay on raw corners.  Throws for a detector without poses.
+  void set_undistort(bool on);
+  bool undistort() const { return undistort_; }
   std::string field_pose_topic() const { return params_.publish_pose_to_topic + "/field"; }
 
   const Params& params() const { return params_; }
@@ -335,6 +340,7 @@ class DetectorCore {
   ImageBuffer preview_buf_;  // page-locked, at_jpeg_max_bytes of the preview: allocated by set_preview
   std::unique_ptr<PublisherQueue<StampedImage>> preview_queue_;
   bool field_layout_ = false;
+  bool undistort_ = false;
   double R_[9], t_[3];
   at_detector* det_ = nullptr;
   std::vector<at_detection> dets_;

@@ -49,6 +49,8 @@ class ApriltagsAmdNode : public rclcpp::Node {
     const int preview_scale = declare_parameter<int>("preview_scale", 0);
     const int preview_quality = declare_parameter<int>("preview_quality", 50);
     const int preview_max_bytes = declare_parameter<int>("preview_max_bytes", 0);
+    // the tag poses (and a field pose) from ideal corners: the calibration's lens distortion undone on the GPU
+    const bool undistort_poses = declare_parameter<bool>("undistort_poses", false);
     // optional override of the share directory (not passed by the launch file)
     std::string share_dir = declare_parameter<std::string>("vision_config_dir", "");
     if (share_dir.empty()) {
@@ -79,6 +81,7 @@ class ApriltagsAmdNode : public rclcpp::Node {
     };
     if (image_jpeg) core_->set_image_jpeg(image_jpeg);
     if (mjpg_device_entropy) core_->set_mjpg_device_entropy(true);  // compressed frames: entropy decode on the GPU
+    if (undistort_poses) core_->set_undistort(true);
     core_->publish_image = [](void* c, const std::vector<uint8_t>& bgr, double stamp_s) {
       auto* self = static_cast<ApriltagsAmdNode*>(c);  // publisher-queue thread
       if (self->core_->image_jpeg()) {  // the payload is the JPEG file

@@ -18,7 +18,8 @@ from .detector import (AT_FMT_BGR8, AT_FMT_GRAY8, AT_FMT_YUYV, TAG_SIZE, TEST_CA
                        AT_CAMCAL_ALL, AT_CAMCAL_CX, AT_CAMCAL_CY, AT_CAMCAL_FX, AT_CAMCAL_FY, AT_CAMCAL_K1, AT_CAMCAL_K2,
                        AT_CAMCAL_K3, AT_CAMCAL_MAX_VIEWS, AT_CAMCAL_P1, AT_CAMCAL_P2, AT_CAMCAL_PINHOLE, CAMCAL_PARAMS,
                        CameraCalibration, CameraCalibrator, CameraCalView,
-                       AT_FIELDMAP_MAX_TAGS, AT_FIELDMAP_MAX_VIEWS, FieldMap, FieldMapper, FieldMapTag, FieldMapView)
+                       AT_FIELDMAP_MAX_TAGS, AT_FIELDMAP_MAX_VIEWS, FieldMap, FieldMapper, FieldMapTag, FieldMapView,
+                       ideal_detections_host, undistort_points_host)
 
 __all__ = ["GpuDetector", "CameraMatrix", "DistCoeffs", "Detection", "Pose", "TagDetection", "load_library",
            "family_entries", "tag_detections", "game_piece_preprocess_device", "TAG_SIZE", "TEST_CAMERA", "TEST_DIST",
@@ -33,4 +34,5 @@ __all__ = ["GpuDetector", "CameraMatrix", "DistCoeffs", "Detection", "Pose", "Ta
            "AT_CAMCAL_MAX_VIEWS", "AT_CAMCAL_FX", "AT_CAMCAL_FY", "AT_CAMCAL_CX", "AT_CAMCAL_CY", "AT_CAMCAL_K1",
            "AT_CAMCAL_K2", "AT_CAMCAL_P1", "AT_CAMCAL_P2", "AT_CAMCAL_K3", "AT_CAMCAL_PINHOLE", "AT_CAMCAL_ALL",
            "CAMCAL_PARAMS", "CameraCalibration", "CameraCalibrator", "CameraCalView",
-           "AT_FIELDMAP_MAX_TAGS", "AT_FIELDMAP_MAX_VIEWS", "FieldMap", "FieldMapper", "FieldMapTag", "FieldMapView"]
+           "AT_FIELDMAP_MAX_TAGS", "AT_FIELDMAP_MAX_VIEWS", "FieldMap", "FieldMapper", "FieldMapTag", "FieldMapView",
+           "ideal_detections_host", "undistort_points_host"]

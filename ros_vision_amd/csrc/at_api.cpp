@@ -59,6 +59,7 @@ bool rig_extrinsics_ok(const at_rig_extrinsics& e);
 void rig_write(const RigRecord& r, at_rig_pose* o);
 // (at_kernels.hip)
 hipError_t launch_rig(const RigBufs& rb, int ninstants, hipStream_t st);
+hipError_t launch_und_points(const UndCam& cam, const double* xy, int n, double* out, uint8_t* ok, hipStream_t st);
 hipError_t launch_rigcal(const CalBufs& b, hipStream_t st);
 hipError_t launch_camcal(const CcBufs& b, hipStream_t st);
 hipError_t launch_fieldmap(const FmBufs& b, hipStream_t st);
@@ -287,6 +288,12 @@ struct at_detector {
   FpRecord* h_field;        // [B] the host side of field.b.hout
   hipEvent_t ev_field[2];   // (created on first use)
   uint64_t field_ns;        // k_field's time of the last collected batch (while profiling)
+  // ideal corners (at_set_undistort): d.und / d.hund, allocated on the first call and kept
+  int last_und;             // the pending / last batch ran with the mode on (h_und holds its records)
+  UndRecord* h_und;         // [B][kDetPoolPerFrame] the host side of d.hund
+  std::vector<std::vector<UndRecord>> und_ovf;  // a frame of more than kDetPoolPerFrame candidates: copied from HBM on demand
+  void* d_undpts;           // at_undistort_points' staging (in, out, flags), grown on demand
+  size_t undpts_cap;        // points it holds
 };
 
 // Experiment and diagnostic knobs (stage cut-offs, grid / tile overrides, phase
@@ -407,6 +414,8 @@ void at_destroy(at_detector* d) {
   for (hipEvent_t e : d->ev_field)
     if (e) (void)hipEventDestroy(e);
   if (d->h_field) (void)hipHostFree(d->h_field);
+  if (d->h_und) (void)hipHostFree(d->h_und);
+  if (d->d_undpts) (void)hipFree(d->d_undpts);
   if (d->h_gp_out) (void)hipHostFree(d->h_gp_out);
   if (d->h_gp_info) (void)hipHostFree(d->h_gp_info);
   if (d->ev_done) (void)hipEventDestroy(d->ev_done);
@@ -870,6 +879,8 @@ static int enqueue(at_detector* d, int nframes, int fmt) {
   d->last_mj_color = 0;  // (at_enqueue_mjpg sets it after a colour-on batch)
   d->mj_ent_batch = 0;   // (... and this after a batch decoded by k_mjpg_entropy)
   d->last_field = d->field_on && d->prm.tag_size > 0;
+  d->last_und = d->prm.undistort && d->prm.tag_size > 0;
+  for (auto& v : d->und_ovf) v.clear();
   d->field_timed = d->last_field && d->profiling;
   d->pending = 1;
   return AT_OK;
@@ -2150,6 +2161,126 @@ int at_field_stats(at_detector* d, uint64_t* out, int cap) {
   return n;
 }
 
+// ---- ideal corners -------------------------------------------------------------
+// The pose stage's head (k_pose, the pose wave of k_decode) maps every candidate's corners
+// through und_point and writes an ideal record per slot beside the detection; the field and
+// rig poses read those.  The side array and its mapped mirror are allocated at the first call;
+// the kernels of a sequence are chosen by Params::undistort, so the captured sequences are
+// dropped whenever it changes.
+int at_set_undistort(at_detector* d, int on) {
+  if (!d || d->pending || !(d->prm.tag_size > 0)) return AT_E_INVALID;
+  on = on ? 1 : 0;
+  if (hipSetDevice(d->device) != hipSuccess) return AT_E_HIP;
+  if (on && !d->d.und) {
+    const size_t B = (size_t)d->B;
+    void* pund = nullptr;
+    UndRecord* hrec = nullptr;
+    void* hdev = nullptr;
+    const bool ok = hipMalloc(&pund, B * kMaxDets * sizeof(UndRecord)) == hipSuccess &&
+                    hipHostMalloc((void**)&hrec, B * kDetPoolPerFrame * sizeof(UndRecord), hipHostMallocMapped) == hipSuccess;
+    int err = ok ? AT_OK : AT_E_NOMEM;
+    if (ok && hipHostGetDevicePointer(&hdev, hrec, 0) != hipSuccess) err = AT_E_HIP;
+    if (err != AT_OK) {
+      if (pund) (void)hipFree(pund);
+      if (hrec) (void)hipHostFree(hrec);
+      return err;
+    }
+    d->allocs.push_back(pund);
+    memset(hrec, 0, B * kDetPoolPerFrame * sizeof(UndRecord));
+    d->h_und = hrec;
+    d->d.und = (UndRecord*)pund;
+    d->d.hund = (UndRecord*)hdev;
+    d->und_ovf.resize(B);
+  }
+  if (d->prm.undistort != on) {
+    d->prm.undistort = on;
+    drop_graphs(d);  // the captured sequences carry the old kernels
+  }
+  return AT_OK;
+}
+
+// (the CPU twins at_ideal_detections_host and at_undistort_points_host: at_undist.cpp)
+
+// the ideal record of result i of `frame` (the candidate's slot in the frame's pool)
+static int und_record(at_detector* d, int frame, int k, const UndRecord** out) {
+  const int ncand = (int)std::min<uint32_t>(d->h_ctrl[kCtlNdets * d->B + frame], kMaxDets);
+  if (ncand <= kDetPoolPerFrame) {
+    *out = d->h_und + (size_t)frame * kDetPoolPerFrame + k;
+    return AT_OK;
+  }
+  std::vector<UndRecord>& v = d->und_ovf[frame];
+  if ((int)v.size() != ncand) {  // (cleared at every enqueue)
+    v.resize(ncand);
+    HIPCHK(hipSetDevice(d->device));
+    HIPCHK(hipMemcpyAsync(v.data(), d->d.und + (size_t)frame * kMaxDets, ncand * sizeof(UndRecord), hipMemcpyDeviceToHost,
+                          d->st));
+    HIPCHK(hipStreamSynchronize(d->st));
+  }
+  *out = v.data() + k;
+  return AT_OK;
+}
+
+int at_ideal_detections(at_detector* d, int frame, at_detection* out, int cap) {
+  if (!d || frame < 0 || frame >= d->last_nframes || (cap > 0 && !out)) return AT_E_INVALID;
+  if (d->pending || !d->last_und) return AT_E_INVALID;
+  const int n = d->res_n[frame];
+  for (int i = 0; i < n && i < cap; i++) {
+    const int k = d->res_idx[(size_t)frame * kMaxDets + i];
+    write_detection(d->res_base[frame][k], out + i);
+    const UndRecord* u = nullptr;
+    const int rc = und_record(d, frame, k, &u);
+    if (rc != AT_OK) return rc;
+    out[i].id = u->id;
+    memcpy(out[i].H, u->H, sizeof(u->H));
+    memcpy(out[i].c, u->c, sizeof(u->c));
+    memcpy(out[i].p, u->p, sizeof(u->p));
+  }
+  return n;
+}
+
+int at_undistort_points(at_detector* d, const double* xy, int n, double* out_xy, uint8_t* ok) {
+  if (!d || n < 0 || n > (1 << 24) || (n > 0 && (!xy || !out_xy || !ok))) return AT_E_INVALID;
+  if (n == 0) return 0;
+  HIPCHK(hipSetDevice(d->device));
+  if ((size_t)n > d->undpts_cap) {
+    size_t cap = std::max<size_t>(1024, d->undpts_cap);
+    while (cap < (size_t)n) cap *= 2;
+    void* p = nullptr;
+    if (hipMalloc(&p, cap * 40) != hipSuccess) return AT_E_NOMEM;  // 16 B in, 16 B out, a flag (in 8)
+    HIPCHK(hipStreamSynchronize(d->st));
+    if (d->d_undpts) (void)hipFree(d->d_undpts);
+    d->d_undpts = p;
+    d->undpts_cap = cap;
+  }
+  double* din = (double*)d->d_undpts;
+  double* dout = din + 2 * d->undpts_cap;
+  uint8_t* dok = (uint8_t*)(dout + 2 * d->undpts_cap);
+  const UndCam c = {d->prm.fx, d->prm.fy, d->prm.cx, d->prm.cy, d->prm.k1, d->prm.k2, d->prm.p1, d->prm.p2, d->prm.k3};
+  HIPCHK(hipMemcpyAsync(din, xy, (size_t)n * 16, hipMemcpyHostToDevice, d->st));
+  HIPCHK(launch_und_points(c, din, n, dout, dok, d->st));
+  HIPCHK(hipMemcpyAsync(out_xy, dout, (size_t)n * 16, hipMemcpyDeviceToHost, d->st));
+  HIPCHK(hipMemcpyAsync(ok, dok, (size_t)n, hipMemcpyDeviceToHost, d->st));
+  HIPCHK(hipStreamSynchronize(d->st));
+  return n;
+}
+
+int at_undistort_stats(at_detector* d, uint64_t* out, int cap) {
+  if (!d || !out || cap < 1) return AT_E_INVALID;
+  if (d->pending) return AT_E_INVALID;
+  uint64_t v[2] = {0, 0};
+  if (d->last_und)
+    for (int f = 0; f < d->last_nframes; f++)
+      for (int i = 0; i < d->res_n[f]; i++) {
+        const UndRecord* u = nullptr;
+        const int rc = und_record(d, f, d->res_idx[(size_t)f * kMaxDets + i], &u);
+        if (rc != AT_OK) return rc;
+        v[u->id < 0 ? 1 : 0]++;
+      }
+  const int n = std::min(cap, 2);
+  for (int i = 0; i < n; i++) out[i] = v[i];
+  return n;
+}
+
 // ---- rig pose ------------------------------------------------------------------
 // The rig owns its stream, its copy of the layout in HBM and one record per instant in HBM and
 // in mapped host memory; of its members it holds pointers only (their candidates, counts and
@@ -2235,6 +2366,7 @@ int at_rig_create(at_detector* const* dets, const at_rig_extrinsics* extr, int n
     v.dets = d->d.dets;
     v.ndets = d->d.ndets;
     v.cam = {d->prm.fx, d->prm.fy, d->prm.cx, d->prm.cy, {}, {}};
+    v.und = nullptr;  // (at_rig_solve sets it)
     memcpy(v.cam.ER, extr[i].R, sizeof(v.cam.ER));
     memcpy(v.cam.Et, extr[i].t, sizeof(v.cam.Et));
   }
@@ -2261,6 +2393,8 @@ int at_rig_solve(at_rig* r, at_rig_pose* out, int cap) {
   if (hipSetDevice(r->device) != hipSuccess) return AT_E_HIP;
   // behind every member's batch (an event of a batch already collected is complete)
   for (int i = 0; i < r->n_cams; i++) HIPCHK(hipStreamWaitEvent(r->st, r->det[i]->ev_done, 0));
+  // a member whose last batch ran with at_set_undistort on is read through its ideal records
+  for (int i = 0; i < r->n_cams; i++) r->b.view[i].und = r->det[i]->last_und ? r->det[i]->d.und : nullptr;
   if (timed) HIPCHK(hipEventRecord(r->ev[0], r->st));
   HIPCHK(launch_rig(r->b, n, r->st));
   if (timed) HIPCHK(hipEventRecord(r->ev[1], r->st));

@@ -8,6 +8,7 @@
 #include "at_fieldpose.h"
 #include "at_rigpose.h"
 #include "at_preview.h"
+#include "at_undist.h"
 
 namespace at {
 
@@ -191,6 +192,7 @@ struct Params {
   int dec_lpq;    // k_decode's lanes per quad in throughput mode (AT_DEC_LPQ, experiment; 0: kDecRowLanes)
   FamilyDesc fam;
   int gp_w, gp_h, gp_c;  // game-piece preprocessing output (at_gp_enable); gp_c == 0: off
+  int undistort;  // at_set_undistort: the pose stage works on ideal corners (at_undist.h) and writes DevBufs::und
 };
 constexpr int kProbeWords = 256;
 
@@ -309,6 +311,7 @@ struct RigCamView {
   const DevDetection* dets;  // [B][kMaxDets]
   const uint32_t* ndets;     // [B]
   RigCam cam;
+  const UndRecord* und;      // [B][kMaxDets] the member's ideal records (at_set_undistort), or null: raw corners
 };
 struct RigBufs {
   RigCamView view[kRigMaxCams];
@@ -367,6 +370,10 @@ struct DevBufs {
   // which replaces two device-to-host copies per batch
   DevDetection* hdets;  // [B][kDetPoolPerFrame] host mirror of each frame's first candidates
   uint32_t* hctrl;      // [ctrl_words] host
+  // ideal records (at_set_undistort; allocated on its first call, null before): slot for slot
+  // beside dets, written by the pose stage, and their host mirror beside hdets
+  UndRecord* und;       // [B][kMaxDets]
+  UndRecord* hund;      // [B][kDetPoolPerFrame] host
   uint32_t* ctrl;       // device control block base
   uint32_t ctrl_words;
   QuadRecord* quads;  // [B][kMaxPairs]  fitted-quad debug record of each kept blob, slot = pair rank

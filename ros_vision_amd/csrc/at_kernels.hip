@@ -2655,11 +2655,14 @@ __device__ void hproject(const double* H, double x, double y, double* ox, double
 // the one-lane restatement (oracle/ao_oracle.c homography_compute2).  The
 // eliminated sub-diagonal entries are never read again and are not zeroed.
 // Returns 0 / -1 (singular), uniform across the wave; H valid on every lane.
-__device__ int homography_wave(const float (*qc)[2], double* A, double* H) {
+// DETP: the corners are a detection record's (at_detection.p: corner i is the image of
+// (und_tx(i), und_ty(i)), doubles -- at_undist.h's und_homography spread over the wave).
+template <typename T, bool DETP = false>
+__device__ int homography_wave(const T (*qc)[2], double* A, double* H) {
   const int lane = (int)lane_id();
   for (int e = lane; e < 72; e += 64) {
     const int row = e / 9, col = e % 9, i = row >> 1;
-    const double c0 = (i == 0 || i == 3) ? -1 : 1, c1 = (i == 0 || i == 1) ? -1 : 1;
+    const double c0 = (i == 0 || i == 3) ? -1 : 1, c1 = ((i == 0 || i == 1) != DETP) ? -1 : 1;
     const double c2 = qc[i][0], c3 = qc[i][1];
     // row 2i: (c0, c1, 1, 0, 0, 0, -c0 c2, -c1 c2, c2); row 2i+1: (0, 0, 0, c0, c1, 1, -c0 c3, -c1 c3, c3)
     const int k = (row & 1) ? col - 3 : col;  // position inside the (c0, c1, 1) triple
@@ -4896,6 +4899,136 @@ struct DecodeShared {
   uint32_t qpre[kMaxBatch + 1];
 };
 
+// ---------------------------------------------------------------------------
+// Ideal corners (at_set_undistort, at_undist.h) at the head of the pose stage: the
+// detection's corners through und_point, its homography recomputed from them, the pose
+// from both; the ideal record {H, c, p, id} goes to DevBufs::und and its host mirror.
+// Three bodies: a wave per detection (und_wave: k_pose<true>, and both waves of
+// k_decode<true>), four lanes per detection (und_homography_quad: k_pose<false>).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ UndCam und_cam(const Params& p) {
+  return UndCam{p.fx, p.fy, p.cx, p.cy, p.k1, p.k2, p.p1, p.p2, p.k3};
+}
+// a wave's LDS for one detection: the corners (raw in, ideal out), the 8 x 9 system, H
+struct UndShared {
+  double q[4][2];
+  double A[72];
+  double H[9];
+};
+// Wave body.  U.q holds the raw corners (stored by this wave, before a team_sync); lanes
+// 0-3 invert one each, in place; H by homography_wave, which is und_homography element by
+// element.  Returns whether the detection is ideal (uniform): all four corners invertible
+// and the system regular; U.q and U.H are then valid on every lane.
+__device__ bool und_wave(const UndCam& cam, UndShared& U) {
+  const int lane = (int)lane_id();
+  bool ok = true;
+  if (lane < 4) {
+    double ou, ov;
+    ok = und_point(cam, U.q[lane][0], U.q[lane][1], &ou, &ov);
+    U.q[lane][0] = ou;
+    U.q[lane][1] = ov;
+  }
+  ok = __all(ok) != 0;
+  team_sync<64>();
+  if (!ok) return false;
+  return homography_wave<double, true>(U.q, U.A, U.H) == 0;
+}
+// Quad body: lane `sub` of a detection's four holds its ideal corner (px, py) and the two
+// rows of the 8 x 9 system that belong to it (rows 2 sub, 2 sub + 1; row g of the system
+// always lives in lane g >> 1, register row g & 1).  Pivot search, row swap and elimination
+// cross the quad by shuffles, and every element goes through und_homography's serial
+// sequence of operations (fct = A[i][col] / A[col][col]; A[i][j] -= fct A[col][j]; the back
+// substitution by the row's owner, its result handed round), so H is bit-identical to the
+// serial form.  Returns false for a singular system (uniform over the quad); the quad's
+// four lanes must all be active.
+__device__ bool und_homography_quad(int sub, double px, double py, double* H) {
+  double r[2][9];
+  und_rows(sub, px, py, r[0], r[1]);
+  bool live = true;
+#pragma unroll
+  for (int col = 0; col < 8; col++) {
+    // pivot: the first row (col..7) holding the strict maximum of |A[row][col]| > 0
+    double v = -1.0;
+    int row = 64;
+#pragma unroll
+    for (int li = 0; li < 2; li++) {
+      const int g = 2 * sub + li;
+      const double a = fabs(r[li][col]);
+      if (g >= col && a > 0.0 && a > v) { v = a; row = g; }
+    }
+#pragma unroll
+    for (int d = 1; d < 4; d <<= 1) {
+      const double ov = __shfl_xor(v, d);
+      const int orow = __shfl_xor(row, d);
+      if (ov > v || (ov == v && orow < row)) { v = ov; row = orow; }
+    }
+    if (!(v >= 1e-10)) { live = false; row = col; }  // singular: the rest runs on, its result unused
+    // the pivot row (from its owner) and row col (from its owner), columns col..8
+    double prow[9], crow[9];
+#pragma unroll
+    for (int j = col; j < 9; j++) {
+      prow[j] = __shfl((row & 1) ? r[1][j] : r[0][j], row >> 1, 4);
+      crow[j] = __shfl(r[col & 1][j], col >> 1, 4);
+    }
+    if (sub == (col >> 1)) {
+#pragma unroll
+      for (int j = col; j < 9; j++) r[col & 1][j] = prow[j];
+    }
+    if (row != col && sub == (row >> 1)) {
+#pragma unroll
+      for (int j = col; j < 9; j++) {
+        if (row & 1) r[1][j] = crow[j];
+        else r[0][j] = crow[j];
+      }
+    }
+#pragma unroll
+    for (int li = 0; li < 2; li++) {
+      if (2 * sub + li > col) {
+        const double fct = r[li][col] / prow[col];
+#pragma unroll
+        for (int j = col + 1; j < 9; j++) r[li][j] = r[li][j] - fct * prow[j];
+      }
+    }
+  }
+  double x[8];
+#pragma unroll
+  for (int col = 7; col >= 0; col--) {
+    double sum = 0;
+#pragma unroll
+    for (int i = col + 1; i < 8; i++) sum = sum + r[col & 1][i] * x[i];
+    x[col] = __shfl((r[col & 1][8] - sum) / r[col & 1][col], col >> 1, 4);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++) H[k] = x[k];
+  H[8] = 1;
+  return live;
+}
+// The ideal record of candidate `slot` (one lane): H and q when `ideal`, else the raw
+// record's values, with id = -1 unless the lens has no distortion (`ident`: a copy).
+__device__ void und_store(const DevBufs& b, uint32_t slot, bool ideal, bool ident, const DevDetection& raw,
+                          const double* H, const double (*q)[2]) {
+  UndRecord u;
+  if (ideal) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) u.H[k] = H[k];
+    und_centre(u.H, u.c);
+#pragma unroll
+    for (int k = 0; k < 4; k++) { u.p[k][0] = q[k][0]; u.p[k][1] = q[k][1]; }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 9; k++) u.H[k] = raw.H[k];
+    u.c[0] = raw.c[0];
+    u.c[1] = raw.c[1];
+#pragma unroll
+    for (int k = 0; k < 4; k++) { u.p[k][0] = raw.p[k][0]; u.p[k][1] = raw.p[k][1]; }
+  }
+  u.id = (ideal || ident) ? raw.id : -1;
+  u.pad = 0;
+  b.und[slot] = u;
+  const uint32_t f = slot / kMaxDets, k = slot % kMaxDets;
+  if (k < (uint32_t)kDetPoolPerFrame) b.hund[f * kDetPoolPerFrame + k] = u;
+}
+
 // POSE: the decode wave's hand-over to the pose wave (LDS): the homography and
 // unrotated corners of quad `seq`, and the pose the pose wave acknowledges with `ack`
 struct PoseHandoff {
@@ -4903,7 +5036,13 @@ struct PoseHandoff {
   double R[9], t[3], err[2];
   uint32_t seq, ack, exit;
 };
-__device__ void pose_worker(PoseHandoff& P, const Params& prm) {
+// UND (at_set_undistort): the pose from ideal corners and the homography recomputed from
+// them (U: this wave's LDS).  The corners handed over are the unrotated ones: the rotated
+// record's are the same four points up to rounding, so its ideal record is computed by
+// the decode wave once the rotation is known (k_decode).  The quarter turn the decode wave
+// applies to R afterwards holds for ideal corners as for raw ones.
+template <bool UND>
+__device__ void pose_worker(PoseHandoff& P, const Params& prm, UndShared* U) {
   const uint32_t lane = lane_id();
   uint32_t seen = 0;
   while (true) {
@@ -4921,6 +5060,20 @@ __device__ void pose_worker(PoseHandoff& P, const Params& prm) {
     for (int k = 0; k < 9; k++) H[k] = P.H[k];
 #pragma unroll
     for (int k = 0; k < 4; k++) { pc[k][0] = P.p[k][0]; pc[k][1] = P.p[k][1]; }
+    if constexpr (UND) {
+      const UndCam cam = und_cam(prm);
+      if (!und_identity(cam)) {
+        if (lane < 4) { U->q[lane][0] = P.p[lane][0]; U->q[lane][1] = P.p[lane][1]; }
+        team_sync<64>();
+        if (und_wave(cam, *U)) {
+#pragma unroll
+          for (int k = 0; k < 9; k++) H[k] = U->H[k];
+#pragma unroll
+          for (int k = 0; k < 4; k++) { pc[k][0] = U->q[k][0]; pc[k][1] = U->q[k][1]; }
+        }
+        team_sync<64>();  // (U is read before the next quad's corners overwrite it)
+      }
+    }
     double R[9], t[3], err[2];
     pose::estimate_tag_pose<true>(H, pc, prm.fx, prm.fy, prm.cx, prm.cy, prm.tag_size, R, t, err, (int)(lane & 3));
     if (lane == 0) {
@@ -5517,8 +5670,17 @@ __device__ __forceinline__ void decode_rows(const DevBufs& b, const Geom& g, con
 // Each instantiation holds the LDS of its own branch only.  (The one-quad body stays in
 // the kernel itself: called as a function of its own it compiled to 80 spilled VGPRs
 // instead of 2.)
-template <bool POSE, int LPQ = 64>
+// UND (with POSE; at_set_undistort): the pose wave works on ideal corners (pose_worker<true>),
+// and the decode wave, once the rotation is decoded and while it would only wait for the pose,
+// computes the record's ideal twin from the record's own (rotated) corners as a wave (und_wave)
+// -- the bits at_ideal_detections_host gives for that record.  Each wave has an UndShared of its own.
+template <bool ON>
+struct UndLds { UndShared u[2]; };
+template <>
+struct UndLds<false> {};
+template <bool POSE, int LPQ = 64, bool UND = false>
 __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_waves_per_eu(POSE ? 1 : AT_DEC_WAVES))) void k_decode(DevBufs b, Geom g, Params prm, int B, int fmt) {
+  static_assert(POSE || !UND, "ideal corners belong to the pose: without the pose wave k_pose computes them");
   if constexpr (LPQ < 64) {
     static_assert(!POSE, "the pose wave goes with one quad per wave");
     decode_rows<LPQ>(b, g, prm, B, fmt);
@@ -5526,13 +5688,15 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
     constexpr int RCAP = kMaxRefineSamples;
     __shared__ DecodeShared S;
     __shared__ PoseHandoff P;
+    __shared__ UndLds<UND> UL;
     const int tid = threadIdx.x;
     kt_begin(b, 10);
     if (POSE) {
       if (tid == 0) { P.seq = 0; P.ack = 0; P.exit = 0; }
       __syncthreads();
       if (tid >= 64) {
-        pose_worker(P, prm);
+        if constexpr (UND) pose_worker<true>(P, prm, &UL.u[1]);
+        else pose_worker<false>(P, prm, nullptr);
         return;
       }
     }
@@ -5940,6 +6104,32 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
         for (int d = 32; d > 0; d >>= 1) bc = min(bc, (uint32_t)__shfl_xor(bc, d));
       }
       } while (false);
+      // UND: the record's ideal twin while the pose wave still works -- the record's corners
+      // (lanes 0-3 restate lane 0's arithmetic below: the rotated H, corner `tid` under it)
+      // through und_wave; und_ideal and the values in UL.u[0] wait for the record's slot
+      bool und_ideal = false;
+      if constexpr (UND) {
+        const UndCam cam = und_cam(prm);
+        if ((float)margin_d >= 0 && bc != 0xffffffffu && !und_identity(cam)) {  // (uniform)
+          UndShared& U = UL.u[0];
+          if (tid < 4) {
+            const int rot = bc >> 24;
+            const double R[9] = {c_rot_c[rot], -c_rot_s[rot], 0, c_rot_s[rot], c_rot_c[rot], 0, 0, 0, 1};
+            double Hr[9];
+            for (int i = 0; i < 3; i++)
+              for (int j = 0; j < 3; j++) {
+                double acc = 0;
+                for (int k = 0; k < 3; k++) acc += S.H[i * 3 + k] * R[k * 3 + j];
+                Hr[i * 3 + j] = acc;
+              }
+            const int tcx = (tid == 1 || tid == 2) ? 1 : -1;
+            const int tcy = (tid < 2) ? 1 : -1;
+            hproject(Hr, tcx, tcy, &U.q[tid][0], &U.q[tid][1]);
+          }
+          team_sync<64>();
+          und_ideal = und_wave(cam, U);
+        }
+      }
       if (POSE) {  // the pose of this quad is done before the next one is handed over
         while (__hip_atomic_load(&P.ack, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seq)
           __builtin_amdgcn_s_sleep(1);
@@ -5987,6 +6177,7 @@ __global__ __launch_bounds__(POSE ? 128 : kDecodeThreads) __attribute__((amdgpu_
             b.dets[slot] = d;
             if (k < (uint32_t)kDetPoolPerFrame) b.hdets[(uint32_t)f * kDetPoolPerFrame + k] = d;
             if (!POSE) b.det_work[atomicAdd(b.det_head, 1u)] = slot;
+            if constexpr (UND) und_store(b, slot, und_ideal, und_identity(und_cam(prm)), d, UL.u[0].H, UL.u[0].q);
           } else {
             atomicOr(b.status + f, kStatusDetsOverflow);  // (more candidates than quads: unreachable)
           }
@@ -6087,7 +6278,12 @@ constexpr int kPoseGroupsPerFrame = 8;  // 128 detections per pass, looped beyon
 // WAVE (latency mode): a whole wave per detection (the quartic's root brackets
 // searched by lane groups, solve_poly_level_wave); else four lanes (a DPP quad)
 // per detection, one bracket each.
-template <bool WAVE>
+// UND (at_set_undistort): the stage's head turns the detection's corners into ideal ones
+// and recomputes H from them (WAVE: und_wave in LDS; else lane `sub` inverts corner `sub`,
+// the corners cross the quad by shuffles and H comes from und_homography_quad); the pose
+// is computed from those, and lane 0 writes the ideal record beside the detection.  A
+// detection with a corner that is not invertible keeps the pose of its raw corners.
+template <bool WAVE, bool UND = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AT_POSE_WAVES))) void k_pose(DevBufs b, Params prm) {
   const int sub = (int)(threadIdx.x % kPoseLanes);
   // the control block is final once k_decode has finished: block 0 hands it to
@@ -6102,8 +6298,55 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AT_POSE_WAVE
     const uint32_t slot = b.det_work[i];
     DevDetection& d = b.dets[slot];
     double R[9], t[3], err[2];
-    pose::estimate_tag_pose<WAVE>(d.H, d.p, prm.fx, prm.fy, prm.cx, prm.cy, prm.tag_size, R, t, err, sub,
-                                  (AT_PROBE_ON(prm) && i == 0 && threadIdx.x == 0) ? b.probe + 16 : nullptr);
+    if constexpr (UND) {
+      const UndCam cam = und_cam(prm);
+      const bool ident = und_identity(cam);
+      double H[9], pc[4][2];
+#pragma unroll
+      for (int k = 0; k < 9; k++) H[k] = d.H[k];
+#pragma unroll
+      for (int k = 0; k < 4; k++) { pc[k][0] = d.p[k][0]; pc[k][1] = d.p[k][1]; }
+      bool ideal = false;
+      if constexpr (WAVE) {
+        __shared__ UndShared U;
+        if (!ident) {
+          if (threadIdx.x < 4) { U.q[threadIdx.x][0] = d.p[threadIdx.x][0]; U.q[threadIdx.x][1] = d.p[threadIdx.x][1]; }
+          team_sync<64>();
+          ideal = und_wave(cam, U);
+          if (ideal) {
+#pragma unroll
+            for (int k = 0; k < 9; k++) H[k] = U.H[k];
+#pragma unroll
+            for (int k = 0; k < 4; k++) { pc[k][0] = U.q[k][0]; pc[k][1] = U.q[k][1]; }
+          }
+          team_sync<64>();  // (U is read before the next detection's corners overwrite it)
+        }
+      } else {
+        if (!ident) {
+          double ou, ov;
+          int ok = und_point(cam, d.p[sub][0], d.p[sub][1], &ou, &ov) ? 1 : 0;
+          ok &= __shfl_xor(ok, 1);
+          ok &= __shfl_xor(ok, 2);
+          double Hq[9];
+          const bool reg = und_homography_quad(sub, ou, ov, Hq);
+          ideal = ok && reg;
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            const double qx = __shfl(ou, k, kPoseLanes), qy = __shfl(ov, k, kPoseLanes);
+            if (ideal) { pc[k][0] = qx; pc[k][1] = qy; }
+          }
+          if (ideal) {
+#pragma unroll
+            for (int k = 0; k < 9; k++) H[k] = Hq[k];
+          }
+        }
+      }
+      pose::estimate_tag_pose<WAVE>(H, pc, prm.fx, prm.fy, prm.cx, prm.cy, prm.tag_size, R, t, err, sub, nullptr);
+      if (WAVE ? threadIdx.x == 0 : sub == 0) und_store(b, slot, ideal, ident, d, H, pc);
+    } else {
+      pose::estimate_tag_pose<WAVE>(d.H, d.p, prm.fx, prm.fy, prm.cx, prm.cy, prm.tag_size, R, t, err, sub,
+                                    (AT_PROBE_ON(prm) && i == 0 && threadIdx.x == 0) ? b.probe + 16 : nullptr);
+    }
     if (WAVE ? threadIdx.x == 0 : sub == 0) {
 #pragma unroll
       for (int k = 0; k < 9; k++) d.pose_R[k] = R[k];
@@ -6160,11 +6403,12 @@ struct FpWave {
 struct FpDevSrc {
   const DevDetection* d;  // the frame's candidate slots
   int count;
+  const UndRecord* u;     // their ideal records (at_set_undistort: ideal p, and id = -1 where not invertible), or null
   __device__ int n() const { return count; }
-  __device__ int32_t id(int c) const { return d[c].id; }
+  __device__ int32_t id(int c) const { return u ? u[c].id : d[c].id; }
   __device__ int32_t hamming(int c) const { return d[c].hamming; }
   __device__ float margin(int c) const { return d[c].decision_margin; }
-  __device__ const double* p(int c) const { return &d[c].p[0][0]; }
+  __device__ const double* p(int c) const { return u ? &u[c].p[0][0] : &d[c].p[0][0]; }
   __device__ const double* pose_R(int c) const { return d[c].pose_R; }
   __device__ const double* pose_t(int c) const { return d[c].pose_t; }
 };
@@ -6172,7 +6416,8 @@ __global__ __launch_bounds__(64) void k_field(DevBufs b, FieldBufs fb, Params pr
   const int f = (int)blockIdx.x;
   if (f >= nframes) return;
   const uint32_t nd = b.ndets[f];
-  const FpDevSrc src = {b.dets + (size_t)f * kMaxDets, (int)(nd < (uint32_t)kMaxDets ? nd : (uint32_t)kMaxDets)};
+  const FpDevSrc src = {b.dets + (size_t)f * kMaxDets, (int)(nd < (uint32_t)kMaxDets ? nd : (uint32_t)kMaxDets),
+                        prm.undistort ? b.und + (size_t)f * kMaxDets : nullptr};
   const FpCam cam = {prm.fx, prm.fy, prm.cx, prm.cy};
   const FpWave w = {(int)threadIdx.x};
   fp_solve_frame(w, src, fb.lay, cam, prm.tag_size, fb.out + f, fb.hout + f);
@@ -6262,7 +6507,8 @@ struct RigDevSrc {
   __device__ FpDevSrc cam(int i) const {
     const RigCamView& v = rb->view[i];
     const uint32_t nd = v.ndets[f];
-    return {v.dets + (size_t)f * kMaxDets, (int)(nd < (uint32_t)kMaxDets ? nd : (uint32_t)kMaxDets)};
+    return {v.dets + (size_t)f * kMaxDets, (int)(nd < (uint32_t)kMaxDets ? nd : (uint32_t)kMaxDets),
+            v.und ? v.und + (size_t)f * kMaxDets : nullptr};
   }
   __device__ RigCam rigcam(int i) const { return rb->view[i].cam; }
 };
@@ -6274,6 +6520,26 @@ __global__ __launch_bounds__(64 * kRigMaxCams) void k_rig(RigBufs rb, int ninsta
   const RigTeam tm = {(int)threadIdx.x};
   rig_solve_instant(tm, src, sh, rb.lay, rb.n_cams, rb.tag_size, rb.out + f, rb.hout + f);
 }
+// ---------------------------------------------------------------------------
+// at_undistort_points: pixels that are no tag corners (a game piece's box centre, for a
+// bearing) through und_point, one thread per pixel.  xy / out: n (u, v) pairs; ok[i] = 0
+// where pixel i is not invertible (out = the raw pixel).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_und_points(UndCam cam, const double* xy, int n, double* out, uint8_t* ok) {
+  const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+  if (i >= n) return;
+  double ou, ov;
+  const bool good = und_point(cam, xy[2 * i], xy[2 * i + 1], &ou, &ov);
+  out[2 * i] = ou;
+  out[2 * i + 1] = ov;
+  ok[i] = good ? 1 : 0;
+}
+hipError_t launch_und_points(const UndCam& cam, const double* xy, int n, double* out, uint8_t* ok, hipStream_t st) {
+  if (n < 1) return hipSuccess;
+  hipLaunchKernelGGL(k_und_points, dim3((n + 63) / 64), dim3(64), 0, st, cam, xy, n, out, ok);
+  return hipGetLastError();
+}
+
 hipError_t launch_rig(const RigBufs& rb, int ninstants, hipStream_t st) {
   hipLaunchKernelGGL(k_rig, dim3(ninstants), dim3(64 * rb.n_cams), 0, st, rb, ninstants);
   return hipGetLastError();
@@ -8046,7 +8312,8 @@ hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, i
     // and nothing is timed -- then the launch is pose-fused (above) and keeps the pose
     // wave's one-quad kernel, as before.
     const bool rows = g.ctw == 64 && !pose_fused && prm.dec_lpq != 64;
-    if (on(10) && pose_fused) hipLaunchKernelGGL(k_decode<true>, grd, dim3(128), 0, st, b, g, prm, B, fmt);
+    if (on(10) && pose_fused && prm.undistort) hipLaunchKernelGGL((k_decode<true, 64, true>), grd, dim3(128), 0, st, b, g, prm, B, fmt);
+    else if (on(10) && pose_fused) hipLaunchKernelGGL(k_decode<true>, grd, dim3(128), 0, st, b, g, prm, B, fmt);
     else if (on(10) && rows) hipLaunchKernelGGL((k_decode<false, kDecRowLanes>), grd, dim3(kDecodeThreads), 0, st, b, g, prm, B, fmt);
     else if (on(10)) hipLaunchKernelGGL(k_decode<false>, grd, dim3(kDecodeThreads), 0, st, b, g, prm, B, fmt);
   }
@@ -8059,7 +8326,10 @@ hipError_t launch_pipeline(const DevBufs& b, const Geom& g, const Params& prm, i
   tk(11, st, 0);
   // latency mode: a wave per detection; throughput mode: four lanes per detection
   if (prm.tag_size > 0 && on(11) && !pose_fused) {
-    if (B < kWideBlobMaxBatch) hipLaunchKernelGGL(k_pose<true>, dim3(32 * B), dim3(64), 0, st, b, prm);
+    // (at_set_undistort: the instantiations whose head makes the corners ideal)
+    if (prm.undistort && B < kWideBlobMaxBatch) hipLaunchKernelGGL((k_pose<true, true>), dim3(32 * B), dim3(64), 0, st, b, prm);
+    else if (prm.undistort) hipLaunchKernelGGL((k_pose<false, true>), dim3(kPoseGroupsPerFrame * B), dim3(64), 0, st, b, prm);
+    else if (B < kWideBlobMaxBatch) hipLaunchKernelGGL(k_pose<true>, dim3(32 * B), dim3(64), 0, st, b, prm);
     else hipLaunchKernelGGL(k_pose<false>, dim3(kPoseGroupsPerFrame * B), dim3(64), 0, st, b, prm);
   }
   tk(11, st, 1);

@@ -56,6 +56,8 @@ EXPORTS = [
     "at_fieldmap_create", "at_fieldmap_add", "at_fieldmap_count", "at_fieldmap_clear", "at_fieldmap_solve",
     "at_fieldmap_solve_host", "at_fieldmap_tags", "at_fieldmap_views", "at_fieldmap_set_profiling",
     "at_fieldmap_stats", "at_fieldmap_destroy",
+    "at_set_undistort", "at_ideal_detections", "at_ideal_detections_host", "at_undistort_points",
+    "at_undistort_points_host", "at_undistort_stats",
 ]
 AT_RIGCAL_MAX_INSTANTS = 4096
 AT_RIGTRACK_MAX_WINDOW = 64
@@ -637,6 +639,15 @@ def load_library(path: str = LIB_PATH):
         L.at_fieldmap_set_profiling.argtypes = [C.c_void_p, C.c_int]
         L.at_fieldmap_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
         L.at_fieldmap_destroy.argtypes = [C.c_void_p]
+    if hasattr(L, "at_set_undistort"):  # (A/B builds of older sources lack the ideal corners)
+        dp, bp = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        L.at_set_undistort.argtypes = [C.c_void_p, C.c_int]
+        L.at_ideal_detections.argtypes = [C.c_void_p, C.c_int, C.POINTER(AtDetection), C.c_int]
+        L.at_ideal_detections_host.argtypes = [C.POINTER(AtCamera), C.POINTER(AtDetection), C.c_int,
+                                               C.POINTER(AtDetection)]
+        L.at_undistort_points.argtypes = [C.c_void_p, dp, C.c_int, dp, bp]
+        L.at_undistort_points_host.argtypes = [C.POINTER(AtCamera), dp, C.c_int, dp, bp]
+        L.at_undistort_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
         L.at_fieldmap_destroy.restype = None
     _LIB = L
     return L
@@ -1037,6 +1048,46 @@ def field_pose_host(detections, poses, tags, max_hamming=0, camera_matrix=None, 
     if rc < 0:
         raise FieldPoseError("at_field_pose_host", rc)
     return _field_pose(out)
+
+
+# ---- ideal corners (at_undist.h) ---------------------------------------------------
+def _at_camera(camera_matrix, distortion_coefficients):
+    cam, dist = camera_matrix or TEST_CAMERA, distortion_coefficients or TEST_DIST
+    return AtCamera(fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy, k1=dist.k1, k2=dist.k2, p1=dist.p1, p2=dist.p2,
+                    k3=dist.k3)
+
+
+def _detections_of(records):
+    return [Detection(id=d.id, hamming=d.hamming, decision_margin=d.decision_margin,
+                      H=np.array(list(d.H)).reshape(3, 3), c=np.array(list(d.c)),
+                      p=np.array([[d.p[k][0], d.p[k][1]] for k in range(4)])) for d in records]
+
+
+def ideal_detections_host(detections, camera_matrix=None, distortion_coefficients=None):
+    """at_ideal_detections_host: the detections with H, c and p from ideal corners -- the lens
+    distortion undone by the exact inverse of the forward model -- and id = -1 (raw values) where
+    a corner is not invertible; on the CPU, bit-equal to GpuDetector.ideal_detections."""
+    arr, n = _detection_records(detections)
+    out = (AtDetection * max(1, n))()
+    c = _at_camera(camera_matrix, distortion_coefficients)
+    _check(load_library().at_ideal_detections_host(C.byref(c), arr, n, out), "at_ideal_detections_host")
+    return _detections_of(out[:n])
+
+
+def _points_in(xy):
+    xy = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
+    return xy, np.empty_like(xy), np.zeros(len(xy), np.uint8)
+
+
+def undistort_points_host(xy, camera_matrix=None, distortion_coefficients=None):
+    """at_undistort_points_host: (n, 2) raw pixels -> ((n, 2) ideal pixels, (n,) bool ok); a pixel
+    that is not invertible comes back raw with ok False.  Bit-equal to GpuDetector.undistort_points."""
+    xy, out, ok = _points_in(xy)
+    c = _at_camera(camera_matrix, distortion_coefficients)
+    dp, bp = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+    _check(load_library().at_undistort_points_host(C.byref(c), xy.ctypes.data_as(dp), len(xy), out.ctypes.data_as(dp),
+                                                   ok.ctypes.data_as(bp)), "at_undistort_points_host")
+    return out, ok.astype(bool)
 
 
 def robot_in_field(field_pose, extrinsic_rotation=None, extrinsic_offset=None):
@@ -1648,6 +1699,7 @@ class GpuDetector:
         self._last = [[] for _ in range(self.max_batch)]
         self._last_status = 0
         self._mjpg_device_entropy = False
+        self.undistort = False
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1840,6 +1892,38 @@ class GpuDetector:
         n = _check(load_library().at_poses(self._h, frame, buf, cap), "at_poses")
         return [Pose(id=b.id, R=np.array(list(b.R)).reshape(3, 3), t=np.array(list(b.t)), err=b.err)
                 for b in buf[:min(n, cap)]]
+
+    # ---- ideal corners (the head of the pose stage) ----------------------------
+    def set_undistort(self, on=True):
+        """at_set_undistort: from the next batch on the tag, field and rig poses come from ideal
+        corners (the lens distortion undone); detections() and the drawings stay raw."""
+        _check(load_library().at_set_undistort(self._h, int(bool(on))), "at_set_undistort")
+        self.undistort = bool(on)
+
+    def ideal_detections(self, frame=0):
+        """at_ideal_detections: `frame`'s detections with H, c and p ideal, same order as
+        detections(frame); id = -1 where a corner is not invertible."""
+        cap = max(self._n[frame], 1)
+        buf = (AtDetection * cap)()
+        n = _check(load_library().at_ideal_detections(self._h, frame, buf, cap), "at_ideal_detections")
+        return _detections_of(buf[:min(n, cap)])
+
+    def undistort_points(self, xy):
+        """at_undistort_points: (n, 2) raw pixels -> ((n, 2) ideal pixels, (n,) bool ok) on the GPU
+        (k_und_points), with this detector's lens."""
+        xy, out, ok = _points_in(xy)
+        dp, bp = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        _check(load_library().at_undistort_points(self._h, xy.ctypes.data_as(dp), len(xy), out.ctypes.data_as(dp),
+                                                  ok.ctypes.data_as(bp)), "at_undistort_points")
+        return out, ok.astype(bool)
+
+    UNDISTORT_STATS = ("ideal", "not_invertible")
+
+    def undistort_stats(self):
+        """at_undistort_stats of the last collected batch."""
+        buf = (C.c_uint64 * len(self.UNDISTORT_STATS))()
+        n = _check(load_library().at_undistort_stats(self._h, buf, len(buf)), "at_undistort_stats")
+        return dict(zip(self.UNDISTORT_STATS, [int(x) for x in buf[:n]]))
 
     # ---- field pose (k_field) ------------------------------------------------
     def set_field_layout(self, tags, max_hamming=0):

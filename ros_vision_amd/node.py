@@ -423,7 +423,8 @@ class ApriltagsDetectorNode:
 
     def __init__(self, width, height, parameters=None, calibration_dir=None, system_config_path=None,
                  publishers=None, device=0, mjpg_color=False, image_jpeg=None, mjpg_device_entropy=False,
-                 preview_scale=0, preview_quality=50, preview_max_bytes=0, field_layout=None, field_max_hamming=0):
+                 preview_scale=0, preview_quality=50, preview_max_bytes=0, field_layout=None, field_max_hamming=0,
+                 undistort=False):
         self.params = dict(PARAMETER_DEFAULTS)
         self.params.update(parameters or {})
         serial = self.params["camera_serial"]
@@ -468,6 +469,11 @@ class ApriltagsDetectorNode:
         self.field_pose_topic = self.pose_topic + "/field"
         if self.field_layout:
             self.detector.set_field_layout(self.field_layout, field_max_hamming)
+        # undistort: the tag, field and rig poses from ideal corners -- the lens distortion of the
+        # calibration file undone on the GPU (at_set_undistort); the detections and drawings stay raw
+        self.undistort = bool(undistort)
+        if self.undistort:
+            self.detector.set_undistort(True)
         self.csv = None
         if self.params["measurement_mode"]:
             path = self.params["timing_csv_path"] or time.strftime("apriltags_timing_%Y%m%d_%H%M%S.csv")
@@ -565,7 +571,9 @@ class RigPoseFuser:
     instant is also added to it, from the nodes' collected detections and poses.
     With a `tracker` (RigTracker over the same cameras, in the nodes' order) every instant is pushed
     to it -- one without a tag too, which its odometry holds -- and the smoothed latest (R, t, cov)
-    (RigTrack) goes out on <publish_pose_to_topic>/rig/tracked."""
+    (RigTrack) goes out on <publish_pose_to_topic>/rig/tracked.
+    A node created with undistort=True hands its ideal detections on (k_rig reads them on the
+    device; the calibrator and the tracker get ideal_detections(0)), the others their raw ones."""
 
     def __init__(self, camera_nodes, field_layout, max_hamming=0, publishers=None, calibrator=None, tracker=None):
         self.nodes = list(camera_nodes)
@@ -583,6 +591,11 @@ class RigPoseFuser:
     def close(self):
         self.solver.close()
 
+    def frames(self):
+        """(detections, poses) of the instant per node: ideal detections where the node undistorts."""
+        return [(n.detector.ideal_detections(0) if getattr(n.detector, "undistort", False) else n.detector.detections(0),
+                 n.detector.poses(0)) for n in self.nodes]
+
     def publish(self, odometry=None, stamp_s=0.0):
         """The RigPose of the instant the nodes last saw (published when it has a tag).  With a
         tracker: `odometry` is RigTracker.push's (None: a new chain), `stamp_s` the instant's time;
@@ -593,9 +606,9 @@ class RigPoseFuser:
             if fn is not None:
                 fn((pose.R, pose.t, pose.cov))
         if self.calibrator is not None:
-            self.calibrator.add([(n.detector.detections(0), n.detector.poses(0)) for n in self.nodes])
+            self.calibrator.add(self.frames())
         if self.tracker is not None:
-            self.tracker.push([(n.detector.detections(0), n.detector.poses(0)) for n in self.nodes], odometry, stamp_s)
+            self.tracker.push(self.frames(), odometry, stamp_s)
             try:
                 self.tracked = self.tracker.solve()
             except FieldPoseError:  # (no tag anywhere in the window yet)

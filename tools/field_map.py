@@ -64,6 +64,8 @@ def main(argv=None):
     ap.add_argument("--family", default="tag36h11")
     ap.add_argument("--max-hamming", type=int, default=0)
     ap.add_argument("--host", action="store_true", help="solve on the CPU twin")
+    ap.add_argument("--undistort", action="store_true",
+                    help="map from ideal corners: the calibration's lens distortion undone on the GPU")
     ap.add_argument("--out", default="field_layout_refined.json")
     args = ap.parse_args(argv)
 
@@ -90,10 +92,12 @@ def main(argv=None):
         if det is None:
             size = (img.shape[1], img.shape[0])
             det = rva.GpuDetector(img.shape[1], img.shape[0], cam, dist, family=args.family, max_batch=1, tag_size=tag_size)
+            if args.undistort:
+                det.set_undistort(True)
         elif (img.shape[1], img.shape[0]) != size:
             raise SystemExit("%s is not %d x %d" % (path, size[0], size[1]))
         det.detect(img, rva.AT_FMT_GRAY8)
-        stored += bool(mapper.add(det.detections(0), det.poses(0), cam))
+        stored += bool(mapper.add(det.ideal_detections(0) if args.undistort else det.detections(0), det.poses(0), cam))
     det.close()
     print("%d of %d frames stored (two map tags or more in the frame)" % (stored, len(paths)), file=sys.stderr)
     if not stored:

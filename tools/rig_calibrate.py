@@ -64,6 +64,8 @@ def main(argv=None):
     ap.add_argument("--max-hamming", type=int, default=0)
     ap.add_argument("--tag-size", type=float, default=None)
     ap.add_argument("--host", action="store_true", help="solve on the CPU twin instead of the GPU")
+    ap.add_argument("--undistort", action="store_true",
+                    help="calibrate from ideal corners: each camera's lens distortion undone on the GPU")
     ap.add_argument("--write", action="store_true", help="save the entries into the system config")
     args = ap.parse_args(argv)
 
@@ -107,9 +109,11 @@ def main(argv=None):
             if cid not in detectors:
                 cm, dist = dets[cid]
                 detectors[cid] = rva.GpuDetector(img.shape[1], img.shape[0], cm, dist, max_batch=1, tag_size=tag_size)
+                if args.undistort:
+                    detectors[cid].set_undistort(True)
             d = detectors[cid]
             d.detect(img, rva.AT_FMT_GRAY8)
-            per.append((d.detections(0), d.poses(0)))
+            per.append((d.ideal_detections(0) if args.undistort else d.detections(0), d.poses(0)))
         stored += bool(cal.add(per))
     print("%d of %d instants stored (two cameras or more with a layout tag)" % (stored, len(groups)), file=sys.stderr)
     if not stored:
