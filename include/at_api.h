@@ -705,6 +705,54 @@ void at_rig_destroy(at_rig *r);
 int at_rig_pose_host(const at_rig_host_cam *cams, int n_cams, const at_field_tag *tags, int n_tags,
                      int max_hamming, double tag_size, at_rig_pose *out);
 
+/* Robust rig pose: the rig pose with Huber weights on the corners and rejection of bad tags, so
+ * that one wrong tag (a layout tag bumped on the field, a false decode, a corner dragged by glare)
+ * does not poison the fused pose.  One kernel (k_rig_robust, launched as k_rig is: one workgroup
+ * per instant, one wave per camera, the rig's own stream); at_rig_solve and at_rig_stats are not
+ * touched by it, and a plain solve after a robust one returns what it returned before.
+ *
+ * Per instant, with s = ru^2 + rv^2 of a corner and k = huber_px:
+ *   cost    rho = s while s <= k^2, else 2 k sqrt(s) - k^2, weight w = 1 resp. k / sqrt(s);
+ *   start   as the rig pose, by the least summed rho;
+ *   fit     the rig pose's 12 LM iterations on the summed rho, each corner's rows of the normal
+ *           equations times its w at the linearisation point;
+ *   reject  at most max_rounds times: a kept tag whose four corners have (s0 + s1) + (s2 + s3) >
+ *           4 reject_px^2 at the current pose is a candidate; none: done; dropping them all would
+ *           leave fewer than min_keep tags (counted per camera view): nothing is dropped,
+ *           starved = 1, done; else all are dropped and the fit runs again from the current pose;
+ *   result  rms_px = sqrt(sum s / (4 n_kept)) over the kept corners, cov = sum w s / (8 n_kept - 6)
+ *           times (J^T W J)^-1, tag_rms_px of every selected tag, dropped ones included.
+ * In the record n_tags, n_cams_used, tags_per_cam and ids are the selection, as at_rig_solve gives
+ * them; steps_taken and rejected are totals over all fits.  In the info: rounds is the number of
+ * rounds that dropped tags (fits run after the first), rejected_mask[c] bit j is set when
+ * ids[c][j] of the record was dropped, huber_cost the final summed rho, n_downweighted the kept
+ * corners beyond huber_px at the final pose.  With huber_px = reject_px = +infinity the record is
+ * at_rig_solve's bit for bit.
+ * Limits: a tag is tested under a pose it helped to fit.  A small displacement among few tags is
+ * absorbed by the pose and is not detected (2 cm in a one-camera view of three tags is not), and
+ * when most tags are wrong the fit follows them and drops the good ones.
+ *
+ * AT_E_INVALID for a NULL config or info, huber_px or reject_px not > 0 (NaN included; +infinity
+ * is valid), max_rounds outside 0..3, min_keep < 1, and whatever at_rig_solve / at_rig_pose_host
+ * refuse.  at_rig_solve_robust writes at most cap records and infos and returns the number of
+ * instants.  at_rig_robust_stats, the last robust solve: [0] instants solved, [1] tags dropped,
+ * [2] rounds run, [3] starved instants, [4] k_rig_robust's time in nanoseconds (as at_rig_stats).
+ * at_rig_pose_robust_host: the same solve on the CPU for one instant, bit-equal record and info. */
+typedef struct { double huber_px, reject_px; int32_t max_rounds, min_keep; } at_rig_robust_config; /* 24 B */
+typedef struct {
+  int32_t n_kept, n_rejected, rounds, starved;
+  uint32_t rejected_mask[AT_RIG_MAX_CAMS];                 /* bit j: ids[cam][j] of the record was dropped */
+  double tag_rms_px[AT_RIG_MAX_CAMS][AT_FIELD_MAX_TAGS];   /* 0 beyond tags_per_cam */
+  double huber_cost;
+  int32_t n_downweighted, pad;                             /* kept corners beyond huber_px at the end */
+} at_rig_robust_info;
+int at_rig_solve_robust(at_rig *r, const at_rig_robust_config *cfg, at_rig_pose *out, at_rig_robust_info *info,
+                        int cap);
+int at_rig_pose_robust_host(const at_rig_host_cam *cams, int n_cams, const at_field_tag *tags, int n_tags,
+                            int max_hamming, double tag_size, const at_rig_robust_config *cfg, at_rig_pose *out,
+                            at_rig_robust_info *info);
+int at_rig_robust_stats(at_rig *r, uint64_t *out, int cap);
+
 /* Rig calibration: the cameras' extrinsics from recorded instants (bundle adjustment).
  *
  * Unknowns: the robot's field pose at every stored instant and, per camera, the rotation

@@ -12,7 +12,7 @@ from .detector import (AT_FMT_BGR8, AT_FMT_GRAY8, AT_FMT_YUYV, TAG_SIZE, TEST_CA
                        AT_GP_MAX_CANDIDATES, GP_BOX_DTYPE, GamePieceBox, GamePieceCapacityError, game_piece_boxes,
                        game_piece_parse_host, preview_host, preview_jpeg_host, preview_size,
                        FieldPose, FieldPoseError, field_pose_host, robot_in_field,
-                       AT_RIG_MAX_CAMS, RigPose, RigSolver, rig_pose_host,
+                       AT_RIG_MAX_CAMS, RigPose, RigSolver, rig_pose_host, RigRobust, RigRobustInfo, rig_pose_robust_host,
                        AT_RIGCAL_MAX_INSTANTS, RigCalibration, RigCalibrator, RigCalInstant,
                        AT_RIGTRACK_MAX_WINDOW, RigTrack, RigTracker, RigTrackInstant,
                        AT_CAMCAL_ALL, AT_CAMCAL_CX, AT_CAMCAL_CY, AT_CAMCAL_FX, AT_CAMCAL_FY, AT_CAMCAL_K1, AT_CAMCAL_K2,
@@ -28,7 +28,8 @@ __all__ = ["GpuDetector", "CameraMatrix", "DistCoeffs", "Detection", "Pose", "Ta
            "GamePieceBox", "GamePieceCapacityError", "game_piece_parse_host", "game_piece_boxes", "GP_BOX_DTYPE",
            "AT_GP_MAX_CANDIDATES", "preview_size", "preview_host", "preview_jpeg_host",
            "FieldPose", "FieldPoseError", "field_pose_host", "robot_in_field",
-           "AT_RIG_MAX_CAMS", "RigPose", "RigSolver", "rig_pose_host",
+           "AT_RIG_MAX_CAMS", "RigPose", "RigSolver", "rig_pose_host", "RigRobust", "RigRobustInfo",
+           "rig_pose_robust_host",
            "AT_RIGCAL_MAX_INSTANTS", "RigCalibration", "RigCalibrator", "RigCalInstant",
            "AT_RIGTRACK_MAX_WINDOW", "RigTrack", "RigTracker", "RigTrackInstant",
            "AT_CAMCAL_MAX_VIEWS", "AT_CAMCAL_FX", "AT_CAMCAL_FY", "AT_CAMCAL_CX", "AT_CAMCAL_CY", "AT_CAMCAL_K1",

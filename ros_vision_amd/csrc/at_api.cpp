@@ -57,8 +57,10 @@ void fp_write(const FpRecord& r, at_field_pose* o);
 // (at_rigpose.cpp)
 bool rig_extrinsics_ok(const at_rig_extrinsics& e);
 void rig_write(const RigRecord& r, at_rig_pose* o);
+bool rig_robust_config(const at_rig_robust_config* c, RigRobustCfg* out);
 // (at_kernels.hip)
 hipError_t launch_rig(const RigBufs& rb, int ninstants, hipStream_t st);
+hipError_t launch_rig_robust(const RigBufs& rb, const RigRobustBufs& xb, int ninstants, hipStream_t st);
 hipError_t launch_und_points(const UndCam& cam, const double* xy, int n, double* out, uint8_t* ok, hipStream_t st);
 hipError_t launch_rigcal(const CalBufs& b, hipStream_t st);
 hipError_t launch_camcal(const CcBufs& b, hipStream_t st);
@@ -2297,6 +2299,14 @@ struct at_rig {
   RigRecord* h_out;          // [B] the host side of b.hout
   int last_n;                // instants of the last solve
   uint64_t ns;               // k_rig's time of the last solve (while profiling)
+  // the robust solve's own records and infos, allocated at the first at_rig_solve_robust: what
+  // at_rig_solve and at_rig_stats read above is never written by it
+  void *xd_out, *xd_info;
+  RigRecord* xh_out;         // [B]
+  RigRobustInfo* xh_info;    // [B]
+  RigRobustBufs xb;
+  int xlast_n;               // instants of the last robust solve
+  uint64_t xns;              // k_rig_robust's time of the last robust solve (while profiling)
 };
 
 void at_rig_destroy(at_rig* r) {
@@ -2307,6 +2317,10 @@ void at_rig_destroy(at_rig* r) {
   if (r->d_tags) (void)hipFree(r->d_tags);
   if (r->d_out) (void)hipFree(r->d_out);
   if (r->h_out) (void)hipHostFree(r->h_out);
+  if (r->xd_out) (void)hipFree(r->xd_out);
+  if (r->xd_info) (void)hipFree(r->xd_info);
+  if (r->xh_out) (void)hipHostFree(r->xh_out);
+  if (r->xh_info) (void)hipHostFree(r->xh_info);
   for (hipEvent_t e : r->ev)
     if (e) (void)hipEventDestroy(e);
   if (r->st) (void)hipStreamDestroy(r->st);
@@ -2419,6 +2433,91 @@ int at_rig_stats(at_rig* r, uint64_t* out, int cap) {
     v[1] += (uint64_t)q.n_tags;
     v[2] += (uint64_t)q.dropped;
     v[3] += (uint64_t)q.rejected;
+  }
+  const int n = std::min(cap, 5);
+  for (int i = 0; i < n; i++) out[i] = v[i];
+  return n;
+}
+
+// ---- robust rig pose -------------------------------------------------------------
+static int rig_robust_reserve(at_rig* r) {
+  if (r->xh_info) return AT_OK;
+  const size_t B = (size_t)r->B;
+  void *ho = nullptr, *hi = nullptr;
+  int err = AT_OK;
+  if (!(hipMalloc(&r->xd_out, B * sizeof(RigRecord)) == hipSuccess &&
+        hipMalloc(&r->xd_info, B * sizeof(RigRobustInfo)) == hipSuccess &&
+        hipHostMalloc((void**)&r->xh_out, B * sizeof(RigRecord), hipHostMallocMapped) == hipSuccess &&
+        hipHostMalloc((void**)&r->xh_info, B * sizeof(RigRobustInfo), hipHostMallocMapped) == hipSuccess))
+    err = AT_E_NOMEM;
+  if (err == AT_OK && !(hipHostGetDevicePointer(&ho, r->xh_out, 0) == hipSuccess &&
+                        hipHostGetDevicePointer(&hi, r->xh_info, 0) == hipSuccess))
+    err = AT_E_HIP;
+  if (err != AT_OK) {  // all or nothing: a later call starts over
+    if (r->xd_out) (void)hipFree(r->xd_out);
+    if (r->xd_info) (void)hipFree(r->xd_info);
+    if (r->xh_out) (void)hipHostFree(r->xh_out);
+    if (r->xh_info) (void)hipHostFree(r->xh_info);
+    r->xd_out = r->xd_info = nullptr;
+    r->xh_out = nullptr;
+    r->xh_info = nullptr;
+    return err;
+  }
+  memset(r->xh_out, 0, B * sizeof(RigRecord));
+  memset(r->xh_info, 0, B * sizeof(RigRobustInfo));
+  r->xb.out = (RigRecord*)r->xd_out;
+  r->xb.hout = (RigRecord*)ho;
+  r->xb.info = (RigRobustInfo*)r->xd_info;
+  r->xb.hinfo = (RigRobustInfo*)hi;
+  return AT_OK;
+}
+
+int at_rig_solve_robust(at_rig* r, const at_rig_robust_config* cfg, at_rig_pose* out, at_rig_robust_info* info,
+                        int cap) {
+  if (!r || cap < 0 || (cap > 0 && (!out || !info))) return AT_E_INVALID;
+  RigRobustCfg c;
+  if (!rig_robust_config(cfg, &c)) return AT_E_INVALID;
+  const int n = r->det[0]->last_nframes;
+  if (n < 1 || n > r->B) return AT_E_INVALID;
+  bool timed = false;
+  for (int i = 0; i < r->n_cams; i++) {
+    if (r->det[i]->last_nframes != n) return AT_E_INVALID;
+    timed = timed || r->det[i]->profiling;
+  }
+  if (hipSetDevice(r->device) != hipSuccess) return AT_E_HIP;
+  const int rc = rig_robust_reserve(r);
+  if (rc != AT_OK) return rc;
+  r->xb.cfg = c;
+  // behind every member's batch, through the members' ideal records where they have them: at_rig_solve's
+  for (int i = 0; i < r->n_cams; i++) HIPCHK(hipStreamWaitEvent(r->st, r->det[i]->ev_done, 0));
+  for (int i = 0; i < r->n_cams; i++) r->b.view[i].und = r->det[i]->last_und ? r->det[i]->d.und : nullptr;
+  if (timed) HIPCHK(hipEventRecord(r->ev[0], r->st));
+  HIPCHK(launch_rig_robust(r->b, r->xb, n, r->st));
+  if (timed) HIPCHK(hipEventRecord(r->ev[1], r->st));
+  HIPCHK(hipStreamSynchronize(r->st));
+  r->xns = 0;
+  if (timed) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, r->ev[0], r->ev[1]));
+    r->xns = (uint64_t)((double)ms * 1e6);
+  }
+  r->xlast_n = n;
+  for (int f = 0; f < n && f < cap; f++) {
+    rig_write(r->xh_out[f], out + f);
+    memcpy(info + f, &r->xh_info[f], sizeof(*info));
+  }
+  return n;
+}
+
+int at_rig_robust_stats(at_rig* r, uint64_t* out, int cap) {
+  if (!r || !out || cap < 1) return AT_E_INVALID;
+  uint64_t v[5] = {0, 0, 0, 0, r->xns};
+  for (int f = 0; f < r->xlast_n; f++) {
+    const RigRobustInfo& q = r->xh_info[f];
+    v[0] += r->xh_out[f].n_tags > 0;
+    v[1] += (uint64_t)q.n_rejected;
+    v[2] += (uint64_t)q.rounds;
+    v[3] += (uint64_t)q.starved;
   }
   const int n = std::min(cap, 5);
   for (int i = 0; i < n; i++) out[i] = v[i];

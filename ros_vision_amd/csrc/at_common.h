@@ -7,6 +7,7 @@
 #include "at_detmath.h"
 #include "at_fieldpose.h"
 #include "at_rigpose.h"
+#include "at_rigrobust.h"
 #include "at_preview.h"
 #include "at_undist.h"
 
@@ -320,6 +321,15 @@ struct RigBufs {
   RigRecord* hout;   // [B] the same in mapped host memory
   double tag_size;
   int n_cams;
+};
+// Robust rig pose (at_rig_solve_robust): k_rig_robust reads the members through the rig's RigBufs
+// and writes here, never to RigBufs::out / hout.
+struct RigRobustBufs {
+  RigRobustCfg cfg;
+  RigRecord* out;        // [B] (HBM)
+  RigRecord* hout;       // [B] mapped host memory
+  RigRobustInfo* info;   // [B] (HBM)
+  RigRobustInfo* hinfo;  // [B] mapped host memory
 };
 
 // Device buffers; every per-frame array is [max_batch][per-frame size].

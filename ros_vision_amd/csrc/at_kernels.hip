@@ -6521,6 +6521,42 @@ __global__ __launch_bounds__(64 * kRigMaxCams) void k_rig(RigBufs rb, int ninsta
   rig_solve_instant(tm, src, sh, rb.lay, rb.n_cams, rb.tag_size, rb.out + f, rb.hout + f);
 }
 // ---------------------------------------------------------------------------
+// Robust rig pose (at_rig_solve_robust): k_rig's shape -- one workgroup per instant, one wave per
+// camera, one lane per corner slot -- over rig_solve_instant_robust of at_rigrobust.h, which
+// at_rig_pose_robust_host runs with one thread.  A tag's four corners are four neighbouring
+// lanes: its S is two shuffles (xor 1, xor 2), a wave's candidate and kept tags one ballot each.
+// Barriers and branches: as k_rig, and the rejection decision (no candidate / starved / drop and
+// fit again) is taken by every thread from the per-camera counts it read from LDS after the same
+// barrier, so the number of rounds is uniform over the workgroup; it may differ between
+// workgroups.  What differs per wave (which of its tags are candidates, its dropped mask) bounds
+// only code without a barrier in it.  Thread 0 stores the record and the info's scalars, each wave
+// its camera's row of tag_rms_px and rejected_mask, to HBM and to the mapped host buffers.
+// ---------------------------------------------------------------------------
+struct RigRobustTeam : RigTeam {
+  __device__ void tag_sum(const double* s, double* S) const {
+    const double a = s[0] + __shfl_xor(s[0], 1);
+    S[0] = a + __shfl_xor(a, 2);
+  }
+  __device__ uint32_t tag_mask(const bool* f) const {
+    const uint64_t b = __ballot(f[0] && (tid & 3) == 0);
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < kFpMaxTags; j++) m |= (uint32_t)((b >> (4 * j)) & 1ull) << j;
+    return m;
+  }
+  __device__ int count(const bool* f) const { return __popcll(__ballot(f[0])); }
+};
+__global__ __launch_bounds__(64 * kRigMaxCams) void k_rig_robust(RigBufs rb, RigRobustBufs xb, int ninstants) {
+  __shared__ RigRobustShared sh;
+  const int f = (int)blockIdx.x;
+  if (f >= ninstants) return;
+  const RigDevSrc src = {&rb, f};
+  RigRobustTeam tm;
+  tm.tid = (int)threadIdx.x;
+  rig_solve_instant_robust(tm, src, sh, rb.lay, rb.n_cams, rb.tag_size, xb.cfg, xb.out + f, xb.hout + f, xb.info + f,
+                           xb.hinfo + f);
+}
+// ---------------------------------------------------------------------------
 // at_undistort_points: pixels that are no tag corners (a game piece's box centre, for a
 // bearing) through und_point, one thread per pixel.  xy / out: n (u, v) pairs; ok[i] = 0
 // where pixel i is not invertible (out = the raw pixel).
@@ -6542,6 +6578,10 @@ hipError_t launch_und_points(const UndCam& cam, const double* xy, int n, double*
 
 hipError_t launch_rig(const RigBufs& rb, int ninstants, hipStream_t st) {
   hipLaunchKernelGGL(k_rig, dim3(ninstants), dim3(64 * rb.n_cams), 0, st, rb, ninstants);
+  return hipGetLastError();
+}
+hipError_t launch_rig_robust(const RigBufs& rb, const RigRobustBufs& xb, int ninstants, hipStream_t st) {
+  hipLaunchKernelGGL(k_rig_robust, dim3(ninstants), dim3(64 * rb.n_cams), 0, st, rb, xb, ninstants);
   return hipGetLastError();
 }
 

@@ -1,7 +1,9 @@
 // at_rigpose.cpp -- at_rig_pose_host: the CPU twin of k_rig over the arithmetic of
-// at_rigpose.h.  Host only (no HIP): one thread holds every slot of every camera, and
-// RigShared, the kernel's LDS block, is a local.
+// at_rigpose.h, and at_rig_pose_robust_host: the twin of k_rig_robust over at_rigrobust.h.
+// Host only (no HIP): one thread holds every slot of every camera, and RigShared, the kernel's
+// LDS block, is a local.
 #include "at_rigpose.h"
+#include "at_rigrobust.h"
 
 #include <string.h>
 
@@ -15,6 +17,8 @@ namespace at {
 
 static_assert(kRigMaxCams == AT_RIG_MAX_CAMS, "at_rigpose.h carries the ABI's camera cap");
 static_assert(sizeof(RigRecord) == sizeof(at_rig_pose), "RigRecord is at_rig_pose");
+static_assert(sizeof(RigRobustCfg) == sizeof(at_rig_robust_config), "RigRobustCfg is at_rig_robust_config");
+static_assert(sizeof(RigRobustInfo) == sizeof(at_rig_robust_info), "RigRobustInfo is at_rig_robust_info");
 
 // (at_fieldpose.cpp)
 int fp_build_layout(const at_field_tag* tags, int n, int16_t* lut, std::vector<FpTag>* out);
@@ -29,6 +33,14 @@ bool rig_extrinsics_ok(const at_rig_extrinsics& e) {
 }
 
 void rig_write(const RigRecord& r, at_rig_pose* o) { memcpy(o, &r, sizeof(*o)); }
+
+// a config as at_rig_solve_robust and at_rig_pose_robust_host take it (NaN thresholds fail `> 0`)
+bool rig_robust_config(const at_rig_robust_config* c, RigRobustCfg* out) {
+  if (!c) return false;
+  const RigRobustCfg r = {c->huber_px, c->reject_px, c->max_rounds, c->min_keep};
+  *out = r;
+  return rig_robust_cfg_ok(r);
+}
 
 namespace {
 struct HostCamSrc {
@@ -78,5 +90,33 @@ extern "C" int at_rig_pose_host(const at_rig_host_cam* cams, int n_cams, const a
   RigRecord rec = {};
   rig_solve_instant(RigHostTeam(), src, *sh, lay, n_cams, tag_size, &rec, (RigRecord*)nullptr);
   rig_write(rec, out);
+  return AT_OK;
+}
+
+extern "C" int at_rig_pose_robust_host(const at_rig_host_cam* cams, int n_cams, const at_field_tag* tags, int n_tags,
+                                       int max_hamming, double tag_size, const at_rig_robust_config* cfg,
+                                       at_rig_pose* out, at_rig_robust_info* info) {
+  if (!out || !info || !cams || n_cams < 1 || n_cams > kRigMaxCams || max_hamming < 0 || n_tags < 1)
+    return AT_E_INVALID;
+  if (!(tag_size > 0) || !std::isfinite(tag_size)) return AT_E_INVALID;
+  RigRobustCfg rc_cfg;
+  if (!rig_robust_config(cfg, &rc_cfg)) return AT_E_INVALID;
+  for (int i = 0; i < n_cams; i++) {
+    const at_rig_host_cam& c = cams[i];
+    if (!c.cam || c.n < 0 || (c.n > 0 && (!c.dets || !c.poses)) || !rig_extrinsics_ok(c.extr)) return AT_E_INVALID;
+  }
+  int16_t lut[kFpMaxIds];
+  std::vector<FpTag> lt;
+  const int rc = fp_build_layout(tags, n_tags, lut, &lt);
+  if (rc != AT_OK) return rc;
+  const FpLayout lay = {lut, lt.data(), max_hamming};
+  const HostRigSrc src = {cams};
+  std::unique_ptr<RigRobustShared> sh(new RigRobustShared());
+  RigRecord rec = {};
+  RigRobustInfo inf = {};
+  rig_solve_instant_robust(RigRobustHostTeam(), src, *sh, lay, n_cams, tag_size, rc_cfg, &rec, (RigRecord*)nullptr,
+                           &inf, (RigRobustInfo*)nullptr);
+  rig_write(rec, out);
+  memcpy(info, &inf, sizeof(*info));
   return AT_OK;
 }

@@ -46,6 +46,7 @@ EXPORTS = [
     "at_preview_jpeg_host", "at_preview_stats",
     "at_set_field_layout", "at_field_poses", "at_field_pose_host", "at_robot_in_field", "at_field_stats",
     "at_rig_create", "at_rig_solve", "at_rig_stats", "at_rig_destroy", "at_rig_pose_host",
+    "at_rig_solve_robust", "at_rig_pose_robust_host", "at_rig_robust_stats",
     "at_rigcal_create", "at_rigcal_add", "at_rigcal_count", "at_rigcal_clear", "at_rigcal_solve",
     "at_rigcal_solve_host", "at_rigcal_instants", "at_rigcal_set_profiling", "at_rigcal_stats", "at_rigcal_destroy",
     "at_rigtrack_create", "at_rigtrack_push", "at_rigtrack_count", "at_rigtrack_clear", "at_rigtrack_solve",
@@ -133,6 +134,18 @@ class AtRigPose(C.Structure):
 class AtRigHostCam(C.Structure):
     _fields_ = [("dets", C.POINTER(AtDetection)), ("poses", C.POINTER(AtPose)), ("n", C.c_int32),
                 ("cam", C.POINTER(AtCamera)), ("extr", AtRigExtrinsics)]
+
+
+class AtRigRobustConfig(C.Structure):
+    _fields_ = [("huber_px", C.c_double), ("reject_px", C.c_double), ("max_rounds", C.c_int32),
+                ("min_keep", C.c_int32)]
+
+
+class AtRigRobustInfo(C.Structure):
+    _fields_ = [("n_kept", C.c_int32), ("n_rejected", C.c_int32), ("rounds", C.c_int32), ("starved", C.c_int32),
+                ("rejected_mask", C.c_uint32 * AT_RIG_MAX_CAMS),
+                ("tag_rms_px", (C.c_double * AT_FIELD_MAX_TAGS) * AT_RIG_MAX_CAMS), ("huber_cost", C.c_double),
+                ("n_downweighted", C.c_int32), ("pad", C.c_int32)]
 
 
 class AtRigcalCamera(C.Structure):
@@ -284,6 +297,34 @@ class RigPose:
     steps_taken: int
     rejected: int
     dropped: int
+
+
+@dataclass
+class RigRobust:
+    """at_rig_robust_config: corners beyond huber_px are down-weighted (Huber), tags whose corner
+    RMS stays beyond reject_px after the fit are dropped and the fit run again, at most max_rounds
+    (0..3) times and never below min_keep tags (counted per camera view).  math.inf for both
+    thresholds is the plain solve."""
+    huber_px: float = 2.0
+    reject_px: float = 6.0
+    max_rounds: int = 3
+    min_keep: int = 2
+
+
+@dataclass
+class RigRobustInfo:
+    """at_rig_robust_info of one instant: dropped[c] lists the ids of camera c's selection (the
+    RigPose's ids[c]) that were dropped, tag_rms_px[c][j] is the corner RMS of ids[c][j] at the
+    final pose (dropped tags included), rounds the number of rounds that dropped tags."""
+    n_kept: int
+    n_rejected: int
+    rounds: int
+    starved: bool
+    rejected_mask: list
+    dropped: list
+    tag_rms_px: list
+    huber_cost: float
+    n_downweighted: int
 
 
 @dataclass
@@ -587,6 +628,13 @@ def load_library(path: str = LIB_PATH):
         L.at_rig_destroy.restype = None
         L.at_rig_pose_host.argtypes = [C.POINTER(AtRigHostCam), C.c_int, C.POINTER(AtFieldTag), C.c_int, C.c_int,
                                        C.c_double, C.POINTER(AtRigPose)]
+    if hasattr(L, "at_rig_solve_robust"):  # (A/B builds of older sources lack the robust rig pose)
+        L.at_rig_solve_robust.argtypes = [C.c_void_p, C.POINTER(AtRigRobustConfig), C.POINTER(AtRigPose),
+                                          C.POINTER(AtRigRobustInfo), C.c_int]
+        L.at_rig_pose_robust_host.argtypes = [C.POINTER(AtRigHostCam), C.c_int, C.POINTER(AtFieldTag), C.c_int, C.c_int,
+                                              C.c_double, C.POINTER(AtRigRobustConfig), C.POINTER(AtRigPose),
+                                              C.POINTER(AtRigRobustInfo)]
+        L.at_rig_robust_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
     if hasattr(L, "at_rigcal_solve"):  # (A/B builds of older sources lack the rig calibration)
         L.at_rigcal_create.argtypes = [C.POINTER(AtRigcalCamera), C.c_int, C.POINTER(AtFieldTag), C.c_int, C.c_int,
                                        C.c_double, C.POINTER(C.c_void_p)]
@@ -1129,13 +1177,28 @@ def _rig_extrinsics(extrinsics, n):
     return arr, len(extrinsics)
 
 
-def rig_pose_host(cameras, tags, max_hamming=0, tag_size=TAG_SIZE):
-    """at_rig_pose_host: the rig pose of one instant on the CPU -- the reference RigSolver.solve is
-    held to.  `cameras` is one (detections, poses, camera_matrix, extrinsics) per camera: the
-    frame's detections() and poses() (same order), its CameraMatrix and its (R, t) with
-    x_robot = R x_cam + t (None: identity).  Raises FieldPoseError for arguments the library
-    refuses."""
-    L = load_library()
+def _rig_robust_config(cfg):
+    """The at_rig_robust_config of a RigRobust (None: a NULL pointer, which the library refuses)."""
+    if cfg is None:
+        return None
+    return AtRigRobustConfig(huber_px=float(cfg.huber_px), reject_px=float(cfg.reject_px),
+                             max_rounds=int(cfg.max_rounds), min_keep=int(cfg.min_keep))
+
+
+def _rig_robust_info(o, pose):
+    masks = [int(x) for x in o.rejected_mask]
+    return RigRobustInfo(n_kept=o.n_kept, n_rejected=o.n_rejected, rounds=o.rounds, starved=bool(o.starved),
+                         rejected_mask=masks,
+                         dropped=[[i for j, i in enumerate(pose.ids[c]) if masks[c] >> j & 1]
+                                  for c in range(AT_RIG_MAX_CAMS)],
+                         tag_rms_px=[[float(x) for x in o.tag_rms_px[c][:pose.tags_per_cam[c]]]
+                                     for c in range(AT_RIG_MAX_CAMS)],
+                         huber_cost=o.huber_cost, n_downweighted=o.n_downweighted)
+
+
+def _rig_host_cams(cameras):
+    """The at_rig_host_cam array of rig_pose_host's `cameras`, its length, and the records it
+    points into."""
     cameras = list(cameras)
     arr = (AtRigHostCam * max(1, len(cameras)))()
     keep = []
@@ -1155,12 +1218,41 @@ def rig_pose_host(cameras, tags, max_hamming=0, tag_size=TAG_SIZE):
         arr[i].dets, arr[i].poses, arr[i].n = darr, parr, n
         arr[i].cam = C.pointer(c)
         arr[i].extr = ext[i]
+    return arr, len(cameras), keep
+
+
+def rig_pose_host(cameras, tags, max_hamming=0, tag_size=TAG_SIZE):
+    """at_rig_pose_host: the rig pose of one instant on the CPU -- the reference RigSolver.solve is
+    held to.  `cameras` is one (detections, poses, camera_matrix, extrinsics) per camera: the
+    frame's detections() and poses() (same order), its CameraMatrix and its (R, t) with
+    x_robot = R x_cam + t (None: identity).  Raises FieldPoseError for arguments the library
+    refuses."""
+    L = load_library()
+    arr, n, _keep = _rig_host_cams(cameras)
     tarr, nt = _field_tags(tags)
     out = AtRigPose()
-    rc = L.at_rig_pose_host(arr, len(cameras), tarr, nt, int(max_hamming), float(tag_size), C.byref(out))
+    rc = L.at_rig_pose_host(arr, n, tarr, nt, int(max_hamming), float(tag_size), C.byref(out))
     if rc < 0:
         raise FieldPoseError("at_rig_pose_host", rc)
     return _rig_pose(out)
+
+
+def rig_pose_robust_host(cameras, tags, cfg, max_hamming=0, tag_size=TAG_SIZE, raw=False):
+    """at_rig_pose_robust_host: the robust rig pose of one instant on the CPU -- the reference
+    RigSolver.solve_robust is held to.  `cameras` and `tags` as rig_pose_host, `cfg` a RigRobust.
+    Returns (RigPose, RigRobustInfo); with raw=True also the two records' bytes."""
+    L = load_library()
+    arr, n, _keep = _rig_host_cams(cameras)
+    tarr, nt = _field_tags(tags)
+    out, info = AtRigPose(), AtRigRobustInfo()
+    c = _rig_robust_config(cfg)
+    rc = L.at_rig_pose_robust_host(arr, n, tarr, nt, int(max_hamming), float(tag_size),
+                                   C.byref(c) if c is not None else None, C.byref(out), C.byref(info))
+    if rc < 0:
+        raise FieldPoseError("at_rig_pose_robust_host", rc)
+    pose = _rig_pose(out)
+    res = (pose, _rig_robust_info(info, pose))
+    return res + (bytes(out), bytes(info)) if raw else res
 
 
 class RigSolver:
@@ -1202,6 +1294,33 @@ class RigSolver:
         buf = (C.c_uint64 * 5)()
         n = _check(load_library().at_rig_stats(self._h, buf, len(buf)), "at_rig_stats")
         names = ("instants_solved", "tags_used", "dropped", "rejected_steps", "kernel_ns")
+        return {k: int(v) for k, v in zip(names[:n], buf)}
+
+    def solve_robust(self, cfg, cap=None, raw=False):
+        """at_rig_solve_robust: one (RigPose, RigRobustInfo) per instant of the members' last batches,
+        `cfg` a RigRobust.  solve() and stats() are not touched by it.  With raw=True each pair is
+        followed by the two records' bytes."""
+        cap = self._cap if cap is None else min(int(cap), self._cap)
+        if getattr(self, "_xbuf", None) is None:
+            self._xbuf = ((AtRigPose * self._cap)(), (AtRigRobustInfo * self._cap)())
+        c = _rig_robust_config(cfg)
+        rc = load_library().at_rig_solve_robust(self._h, C.byref(c) if c is not None else None, self._xbuf[0],
+                                                self._xbuf[1], cap)
+        if rc < 0:
+            raise FieldPoseError("at_rig_solve_robust", rc)
+        self.instants = rc
+        out = []
+        for f in range(min(rc, cap)):
+            pose = _rig_pose(self._xbuf[0][f])
+            one = (pose, _rig_robust_info(self._xbuf[1][f], pose))
+            out.append(one + (bytes(self._xbuf[0][f]), bytes(self._xbuf[1][f])) if raw else one)
+        return out
+
+    def robust_stats(self):
+        """at_rig_robust_stats of the last solve_robust."""
+        buf = (C.c_uint64 * 5)()
+        n = _check(load_library().at_rig_robust_stats(self._h, buf, len(buf)), "at_rig_robust_stats")
+        names = ("instants_solved", "tags_dropped", "rounds", "starved", "kernel_ns")
         return {k: int(v) for k, v in zip(names[:n], buf)}
 
     def close(self):

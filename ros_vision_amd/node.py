@@ -573,9 +573,13 @@ class RigPoseFuser:
     to it -- one without a tag too, which its odometry holds -- and the smoothed latest (R, t, cov)
     (RigTrack) goes out on <publish_pose_to_topic>/rig/tracked.
     A node created with undistort=True hands its ideal detections on (k_rig reads them on the
-    device; the calibrator and the tracker get ideal_detections(0)), the others their raw ones."""
+    device; the calibrator and the tracker get ideal_detections(0)), the others their raw ones.
+    With `robust` (a RigRobust) the published record is RigSolver.solve_robust's, its RigRobustInfo
+    is kept in self.robust_info, and the calibrator and the tracker get the frames without the
+    detections (and their poses) of the tags that solve dropped."""
 
-    def __init__(self, camera_nodes, field_layout, max_hamming=0, publishers=None, calibrator=None, tracker=None):
+    def __init__(self, camera_nodes, field_layout, max_hamming=0, publishers=None, calibrator=None, tracker=None,
+                 robust=None):
         self.nodes = list(camera_nodes)
         self.field_layout = load_field_layout(field_layout)
         self.solver = RigSolver([n.detector for n in self.nodes],
@@ -587,28 +591,46 @@ class RigPoseFuser:
         self.tracker = tracker
         self.tracked_pose_topic = self.rig_pose_topic + "/tracked"
         self.tracked = None
+        self.robust = robust
+        self.robust_info = None
 
     def close(self):
         self.solver.close()
 
-    def frames(self):
-        """(detections, poses) of the instant per node: ideal detections where the node undistorts."""
-        return [(n.detector.ideal_detections(0) if getattr(n.detector, "undistort", False) else n.detector.detections(0),
-                 n.detector.poses(0)) for n in self.nodes]
+    def frames(self, info=None):
+        """(detections, poses) of the instant per node: ideal detections where the node undistorts.
+        With `info`, the RigRobustInfo of a robust solve of this same instant (publish() passes its
+        own), without the tags that solve dropped: per camera every detection of a dropped id goes,
+        a second detection of that id which the selection passed over too -- it is the tag that is
+        wrong, and the next selection would pick that one up."""
+        out = [(n.detector.ideal_detections(0) if getattr(n.detector, "undistort", False) else n.detector.detections(0),
+                n.detector.poses(0)) for n in self.nodes]
+        if info is None:
+            return out
+        kept = []
+        for (dets, poses), gone in zip(out, info.dropped):
+            keep = [i for i, d in enumerate(dets) if d.id not in gone]
+            kept.append(([dets[i] for i in keep], [poses[i] for i in keep]))
+        return kept
 
     def publish(self, odometry=None, stamp_s=0.0):
         """The RigPose of the instant the nodes last saw (published when it has a tag).  With a
         tracker: `odometry` is RigTracker.push's (None: a new chain), `stamp_s` the instant's time;
         the tracked pose is kept in self.tracked (None while the window has no tag)."""
-        pose = self.solver.solve()[0]
+        if self.robust is not None:
+            pose, self.robust_info = self.solver.solve_robust(self.robust)[0]
+        else:
+            pose = self.solver.solve()[0]
         if pose.n_tags:
             fn = self.publishers.get(self.rig_pose_topic)
             if fn is not None:
                 fn((pose.R, pose.t, pose.cov))
+        # (the frames of the instant just solved, filtered by that solve's own info)
+        handed = self.frames(self.robust_info) if self.calibrator is not None or self.tracker is not None else None
         if self.calibrator is not None:
-            self.calibrator.add(self.frames())
+            self.calibrator.add(handed)
         if self.tracker is not None:
-            self.tracker.push(self.frames(), odometry, stamp_s)
+            self.tracker.push(handed, odometry, stamp_s)
             try:
                 self.tracked = self.tracker.solve()
             except FieldPoseError:  # (no tag anywhere in the window yet)
